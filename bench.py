@@ -15,14 +15,27 @@ Workloads (Quadrotor CPDP with time-warping, n_grid "horizon" 50, 4 RK4 steps pe
       and loss are all-reduced over the ranks (RCCL over xGMI) and the all-reduced gradient drives the single update.
 `value` = trajectories * K / wall seconds over all ranks (trajectory outer-iterations per second, whole job).
 
+The learner is one run of the example's length (WORKLOADS `outer_iters`: quad_example.py:63 runs 50 Nesterov iterations,
+robotarm_random.py:67 100, rocket_groundtruth.py:92 1000).  Warmup + K beyond that starts the run again from the same seeds
+(parameters and optimizer state as at iteration 0), so every step is an outer iteration of the example's run.  Without the
+restart the fixed-rate iteration drives the cost weights of some quadrotor seeds through zero from ~170 outer iterations on:
+their solves fail and their gradients and parameters become NaN (profiles/r06_w_long_runs.txt).
+
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f32|f64] [--mode independent|shared]
-                    [--config quadrotor|robotarm|rocket]
+                    [--config quadrotor|robotarm|rocket] [--dump-outputs DIR] [--full]
 
 `--config` selects another BASELINE configuration with the same JSON schema (WORKLOADS below): `robotarm` = configs[1]
 (Examples/robotarm_random.py:14-73: n_grid 50, 1024 random seeds, fp32, plain gradient steps at lr 0.1), `rocket` =
 configs[4] at one GPU's shard (Examples/rocket_groundtruth.py:14-111: n_grid 100, 8192 / 8 = 1024 seeds, fp32 solve +
-fp64 auxiliary pass, ground-truth waypoints, lr 1e-3).  The default line (quadrotor, fp32, N = 1) also carries an
-`"f64"` object: the same workload run for 5 steps at the reference's own precision after the timed region.
+fp64 auxiliary pass, ground-truth waypoints, lr 1e-3).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figures + `config`, whose per-kernel times
+come from HIP events of the timed steps themselves).  `--full` adds what takes work of its own: the `roofline` object
+(operation-count model + committed counter folds), on the default line (quadrotor, fp32, N = 1) an `"f64"` object -- the
+same workload run for 5 steps at the reference's own precision after the timed region --, and at N = 1 `cpu_baseline`
+and `parity_vs_oracle` (the oracle on a sample of the run's own seeds).
+`--dump-outputs DIR` writes what the last timed step computed (loss, grad, theta, state_grid, control_grid) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no torch.distributed.run environment: this process touches no GPU, starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child, relays rank 0's JSON line and exits
@@ -45,13 +58,13 @@ PROFILE_TAG = "r06"            # profiles/<tag>_hbm_traffic.json, <tag>_issue_co
 # The workloads of BASELINE.json's configs that bench.py can emit a line for.  `batch` is per GPU.
 WORKLOADS = {
     "quadrotor": dict(kind="quadrotor", n_grid=50, batch=4096, dtype="f32", aux_dtype=None, method="Nesterov", lr=1e-2,
-                      spread=None, baseline="configs[2]", cpu_seeds=64, cpu_workers=64,
+                      outer_iters=50, spread=None, baseline="configs[2]", cpu_seeds=64, cpu_workers=64,
                       what="Quadrotor (JinEnv, initCost_Polynomial, beta time-warp) CPDP"),
     "robotarm": dict(kind="robotarm", n_grid=50, batch=1024, dtype="f32", aux_dtype=None, method="Vanilla", lr=1e-1,
-                     spread=0.05, baseline="configs[1]", cpu_seeds=64, cpu_workers=64,
+                     outer_iters=100, spread=0.05, baseline="configs[1]", cpu_seeds=64, cpu_workers=64,
                      what="RobotArm 2-link (JinEnv, initCost_Polynomial, beta time-warp) CPDP, Examples/robotarm_random.py:14-73"),
     "rocket": dict(kind="rocket", n_grid=100, batch=1024, dtype="f32", aux_dtype="f64", method="Vanilla", lr=1e-3,
-                   spread=0.05, baseline="configs[4] (one GPU's shard of 8192 / 8)", cpu_seeds=16, cpu_workers=16,
+                   outer_iters=1000, spread=0.05, baseline="configs[4] (one GPU's shard of 8192 / 8)", cpu_seeds=16, cpu_workers=16,
                    what="Rocket 6-DoF (JinEnv, initCost2, beta time-warp) CPDP, Examples/rocket_groundtruth.py:14-111, "
                         "fp32 OC solve + fp64 auxiliary (Riccati / sensitivity) pass, waypoints from the true parameters"),
 }
@@ -69,7 +82,7 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="trajectories per GPU (default: the configuration's)")
     ap.add_argument("--n-grid", type=int, default=None)
     ap.add_argument("--dtype", default=None, choices=["f32", "f64"], help="arithmetic of the OC solve (default: the configuration's)")
-    ap.add_argument("--no-f64-leg", action="store_true", help="skip the 5 fp64 steps appended to the default fp32 headline line")
+    ap.add_argument("--no-f64-leg", action="store_true", help="--full: skip the 5 fp64 steps appended to the default fp32 headline line")
     ap.add_argument("--substeps", type=int, default=0,
                     help="minimum split units per grid interval of the auxiliary sweeps (0: library default = 1 with error control)")
     ap.add_argument("--aux-rtol", type=float, default=1e-3,
@@ -77,7 +90,11 @@ def parse_args(argv=None):
                          "(scipy default rtol 1e-3, CPDP.py:335,368); 0 = fixed --substeps (round 1: --substeps 4 --aux-rtol 0)")
     ap.add_argument("--mode", default=None, choices=["independent", "shared"],
                     help="default: independent seeds at N=1 (configs[2]), shared theta + gradient all-reduce at N>1 (configs[3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline, the fp64 leg, the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
     ap.add_argument("--cpu-seeds", type=int, default=0, help="seeds of the CPU baseline sample (default 64)")
     ap.add_argument("--library", default=None, help="tuning only: path of an alternative build of the model library")
     ap.add_argument("--warm-start", action="store_true",
@@ -265,9 +282,21 @@ def build_learner(args, oc, d, lib, rank, world, mode, w=None, pg=None):
     return L, demos["theta0"][None, :], demos["x0"]
 
 
-def timed_steps(L, steps, warmup, sync, torch):
+def restart(L, theta_init):
+    """Start the learner's run again: initial parameters, zero optimizer state, iteration 0, cold-started solves -- the state
+    of a new SparseDemoLearner on the same seeds."""
+    L.theta.copy_(theta_init)
+    for t in (L.m, L.v, L.vhat):
+        t.zero_()
+    L.iter_idx = 0
+    L._sol = None
+
+
+def timed_steps(L, steps, warmup, sync, torch, last=None, run=None):
     """`warmup` untimed steps, then exactly `steps` steps between two synchronisations, every kernel of a step bracketed
-    by HIP events on the stream it is launched on (torch's current stream).  -> (seconds, {kernel: ms per step}, last loss)"""
+    by HIP events on the stream it is launched on (torch's current stream).  -> (seconds, {kernel: ms per step}, last loss);
+    `last` (a dict), if given, receives the (loss, grad) the last step returned; `run` = (outer iterations per run, initial
+    parameters), if given: the learner restarts when it has done a run's iterations."""
     import numpy as np
     names = ("oc_solve", "aux_riccati", "aux_forward", "update")
     ev = {k: [] for k in names}
@@ -279,19 +308,50 @@ def timed_steps(L, steps, warmup, sync, torch):
         if cur.get("prev"):
             ev[cur["prev"][0]].append((cur["prev"][1], e))
         cur["prev"] = None if name == "end" else (name, e)
+
+    def step():
+        if run is not None and L.iter_idx == run[0]:
+            restart(L, run[1])
+        return L.step()
     for _ in range(warmup):
-        L.step()
+        step()
     sync()
     L.event_hook = hook
     t0 = time.perf_counter()
     loss = None
     for _ in range(steps):
-        loss, _g = L.step()
+        loss, _g = step()
     sync()
     elapsed = time.perf_counter() - t0
     L.event_hook = None
     ktime = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}    # ms per step
+    if last is not None:
+        last.update(loss=loss, grad=_g)
     return elapsed, ktime, loss
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """`--dump-outputs`: every array as out_dir/<name>.npy in its own precision (float32 / float64; anything else as
+    float64).  If the whole exceeds `limit` bytes, the arrays with one row per trajectory keep the same fixed sample of
+    rows (seeded, sorted) -- the same rows from run to run, so that two builds compare row for row.  -> {name: shape}"""
+    import numpy as np
+    arrs = {}
+    for k, v in arrays.items():
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrs.values())
+    B = max(a.shape[0] if a.ndim else 1 for a in arrs.values())
+    if total > limit and B > 1:
+        keep = max(1, int(B * limit // total))
+        rows = np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+        arrs = {k: (a[rows] if a.ndim and a.shape[0] == B else a) for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def lean_level0(args):
@@ -383,7 +443,7 @@ def main(argv=None):
         dist.init_process_group(args.backend, rank=rank, world_size=world)       # "nccl" == RCCL on ROCm
 
     import lfsd_amd  # noqa: F401
-    from lfsd_amd import models, perf_model
+    from lfsd_amd import models
     TD = {"f32": torch.float32, "f64": torch.float64}
     dtype = TD[args.dtype]
     aux_name = w["aux_dtype"] if args.dtype == w["dtype"] else None      # (an explicit --dtype f64 runs everything in fp64)
@@ -411,7 +471,7 @@ def main(argv=None):
     # HIP results of the first seeds at theta_0, kept for the cross-check against the CPU baseline's oracle results
     n_chk = 4
     chk_loss = chk_grad = None
-    if mode == "independent" and rank == 0:
+    if args.full and mode == "independent" and rank == 0:
         sol_c = oc.cocSolverBatch(x0[:n_chk], d["horizon"], theta0[:n_chk])
         aux_c = oc.auxSysSolverBatch(sol_c, d["taus"], d["waypoints"], d["interface"])
         chk_loss, chk_grad = aux_c["loss"].double().cpu().numpy(), aux_c["grad"].double().cpu().numpy()
@@ -421,65 +481,27 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    elapsed, ktime, loss = timed_steps(L, args.steps, args.warmup, sync, torch)
+    last = {}
+    run = (w["outer_iters"], L.theta.clone())
+    elapsed, ktime, loss = timed_steps(L, args.steps, args.warmup, sync, torch, last, run)
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: SparseDemoLearner.step's (loss, grad), the parameters
+        # it left in the learner, and the state / control grids of the optimal-control solve it differentiated
+        dump_outputs(args.dump_outputs, dict(loss=last["loss"], grad=last["grad"], theta=L.theta,
+                                             state_grid=L._sol["state_grid"], control_grid=L._sol["control_grid"]))
 
     st = L._sol["status"].cpu().numpy()
     it = L._sol["iters"].cpu().numpy()
     if rank == 0:
-        n, m, p, nc = lib.n_state, lib.n_control, lib.n_auxvar, lib.n_const
-        dom = max(("oc_solve", "aux_riccati", "aux_forward"), key=lambda k: ktime[k])
-        nw, ni = L.taus.shape[1], len(d["interface"])
         stats = L._aux["stats"].double().cpu().numpy()
         units = {"aux_riccati": float(stats[:, 0].mean()) / args.n_grid, "aux_forward": float(stats[:, 2].mean()) / args.n_grid}
-        it_seed = seed_iterations(models, torch, w, args, L, dev) if seeded_f64(args, args.dtype, dom, args.warm_start) else None
-        useful_tflops, mfma_tflops, useful_flops, dom_dtype, valu_frac = kernel_model(perf_model, oc.model_spec(), args, args.dtype, aux_name, dom,
-                                                                                      ktime, float(it.mean()), units, B, args.warm_start, it_seed)
-        es = 4 if dom_dtype == "f32" else 8
-        abytes = B * algorithmic_bytes(dom, n, m, p, nc, args.n_grid, nw, ni, es)
-        achieved = abytes / (ktime[dom] * 1e-3) / 1e9
-        # PMC passes are separate rocprofv3 runs (tools/hbm_traffic.py, tools/issue_counters.py); the figures only apply
-        # to the workload they were collected on, so they are attached to the configuration's default command and null otherwise
+        # the configuration's default command (the one the committed counter folds and the fp64 leg belong to)
         default_cmd = (B == w["batch"] and args.n_grid == w["n_grid"] and args.dtype == w["dtype"] and args.substeps == 0
                        and args.aux_rtol == 1e-3 and mode == "independent" and not args.warm_start and not args.library)
-        tag = PROFILE_TAG if args.config == "quadrotor" else "%s_%s" % (PROFILE_TAG, args.config)
-        sources = {}
-
-        def profile(name, key=None):
-            """Counter figures that THIS run does not measure: read from a committed fold of separate rocprofv3 --pmc passes
-            of the same command, and named as such in the line (file + git blob hash of the file read, and the commit the
-            fold was collected at when the fold records it)."""
-            import hashlib
-            rel = "profiles/%s_%s.json" % (tag, name)
-            path = os.path.join(ROOT, rel)
-            if not (default_cmd and os.path.exists(path)):
-                return {}
-            try:
-                raw = open(path, "rb").read()
-                js = json.loads(raw)
-                sources[name] = {"file": rel, "git_blob": hashlib.sha1(b"blob %d\0" % len(raw) + raw).hexdigest(),
-                                 "collected_at_commit": js.get("collected_at_commit")}
-                if key:
-                    return js.get(key) or {}
-                return js.get(dom) or (js.get("oc_solve_wide", {}) if dom == "oc_solve" else {})      # (models solved on the wide mapping)
-            except Exception:
-                return {}
-        traffic = profile("hbm_traffic").get("hbm_bytes_per_launch")
-        if traffic is not None and it_seed is not None:      # the fp32-seeded fp64 solve: both kernels of `oc_solve` move bytes
-            traffic += profile("hbm_traffic", "oc_solve_seed_f32").get("hbm_bytes_per_launch") or 0.0
-        issue = profile("issue_counters")
-        executed = issue.get("valu_flops_executed_per_launch")
-        if dom == "oc_solve":      # a two-launch wide solve (round 6): `oc_solve` is both launches, the folds keep the four-wavefront one apart
-            w4 = profile("hbm_traffic", "oc_solve_wide_w4").get("hbm_bytes_per_launch")
-            if traffic is not None and w4:
-                traffic += w4
-            w4 = profile("issue_counters", "oc_solve_wide_w4").get("valu_flops_executed_per_launch")
-            if executed is not None and w4:
-                executed += w4
-        peak = VALU_PEAK_TFLOPS[dom_dtype]
         out = {
             "metric": "CPDP outer iterations/sec (batch trajectories)",
             "value": B * world * args.steps / elapsed,
@@ -497,7 +519,7 @@ def main(argv=None):
                                     "BASELINE configs[3] at 4096 per GPU: random demonstrations (start, goal, waypoints), ONE "
                                     "shared theta, summed d(theta)+loss all-reduced over the ranks every iteration and "
                                     "driving the update (SparseDemoLearner mode='shared')"),
-                       "name": args.config, "mode": mode, "batch_per_gpu": B, "n_grid": args.n_grid, "steps_per_grid": 4,
+                       "name": args.config, "mode": mode, "batch_per_gpu": B, "outer_iters_per_run": w["outer_iters"], "n_grid": args.n_grid, "steps_per_grid": 4,
                        # backend of the initialised torch.distributed group the shared-mode all-reduce went through (None: no group)
                        "process_group": (str(dist.get_backend()) if dist.is_initialized() else None),
                        "aux_substeps": args.substeps, "aux_rtol": args.aux_rtol,
@@ -514,79 +536,127 @@ def main(argv=None):
                        # N>1 test compares it with a single-process run over the union of the ranks' demonstrations)
                        "theta": [float(x) for x in L.theta.double().cpu().numpy().ravel()] if mode == "shared" else None,
                        "n_unconverged_last_step": (int(round(float(L.n_bad_device.item()))) if (mode == "shared" and L.n_bad_device is not None) else None)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": abytes, "avg_launch_ms": ktime[dom],
-                         # the fraction that actually bounds this path: vector issue, not HBM
-                         "valu_useful_tflops": useful_tflops,
-                         "valu_frac": valu_frac, "valu_peak_tflops": peak, "kernel_dtype": dom_dtype,
-                         "seed_iters_mean_f32": it_seed,
-                         # what the vector pipe EXECUTED per launch by the counters (every enabled lane, redundant group-uniform
-                         # work included) at this run's launch time, and the modelled useful share of it
-                         "valu_executed_tflops": None if executed is None else executed / (ktime[dom] * 1e-3) / 1e12,
-                         "valu_useful_over_executed": None if executed is None else useful_flops / executed,
-                         "mfma_useful_tflops": mfma_tflops,
-                         "valu_issue_util": issue.get("valu_issue_util"),
-                         "valu_lane_util": issue.get("valu_lane_util"),
-                         "mfma_busy": issue.get("mfma_busy"),
-                         "source": sources or None,
-                         "note": "the per-trajectory recursions are latency/VALU-issue bound, not HBM bound: "
-                                 "algorithmic bytes are O(10 KB) per trajectory against O(10^7) FLOP of sequential "
-                                 "vector work per solve; valu_frac = useful VECTOR flops (perf_model.py, checked against the "
-                                 "counters in round 3) / the vector peak of the kernel's arithmetic (157.3 fp32, 78.6 fp64 TFLOP/s); "
-                                 "traffic, valu_issue_util, valu_lane_util (EXEC-enabled lanes per vector instruction) and "
-                                 "mfma_busy are NOT measured by this run: they come from the committed fold of separate rocprofv3 "
-                                 "--pmc passes of this command named in `source` (null when the run is not the configuration's "
-                                 "default command or no fold is committed for it); see DESIGN.md section 4"},
         }
-        # the reference computes in fp64 throughout (CPDP.py:183, :329): the same workload at that precision, 5 steps after the
-        # timed region of the default fp32 headline line -- a reported figure beside `value`, which stays the fp32 rate
-        if (args.config == "quadrotor" and default_cmd and world == 1 and not args.no_f64_leg):
-            try:
-                oc.setDevice(dev, torch.float64)
-                L64, _, _ = build_learner(args, oc, d, lib, rank, world, mode, w)
-                L64.count_unconverged = False
-                e64, k64, _ = timed_steps(L64, 5, 1, sync, torch)
-                st64 = L64._aux["stats"].double().cpu().numpy()
-                u64 = {"aux_riccati": float(st64[:, 0].mean()) / args.n_grid, "aux_forward": float(st64[:, 2].mean()) / args.n_grid}
-                d64 = max(("oc_solve", "aux_riccati", "aux_forward"), key=lambda k: k64[k])
-                it64 = float(L64._sol["iters"].double().mean().item())
-                a64 = argparse.Namespace(**dict(vars(args), dtype="f64"))
-                seed64 = float(it.mean()) if seeded_f64(a64, "f64", d64, False) else None      # (the fp32 leg's own solves: same seeds, same rule)
-                uf64, _, _, _, frac64 = kernel_model(perf_model, oc.model_spec(), a64, "f64", None, d64, k64, it64, u64, B, False, seed64)
-                out["f64"] = {"value": B * 5 / e64, "unit": "trajectory outer-iterations/s", "steps": 5, "warmup": 1,
-                              "ms_per_step": e64 / 5 * 1e3, "kernel_ms": {k: round(v, 3) for k, v in k64.items()},
-                              "aux_units_per_interval": {k: round(v, 3) for k, v in u64.items()},
-                              "oc_status_hist": np.bincount(L64._sol["status"].cpu().numpy(), minlength=5).tolist(),
-                              "kernel": d64, "valu_useful_tflops": uf64, "valu_frac": frac64,
-                              "oc_iters_mean": it64, "oc_seed_iters_mean_f32": seed64,
-                              "note": "same seeds, every returned number and every convergence test in fp64 (the reference's precision); "
-                                      "the cold OC solve is seeded by the fp32 solve of the same problem (lfsd_capi.cpp, coc_solve_seeded; "
-                                      "oc_iters_mean counts both), so `oc_solve` is an fp32 and an fp64 kernel and valu_frac prices each "
-                                      "part at the vector peak of its arithmetic; model-only utilisation"}
-                del L64
-            except Exception as exc:
-                out["f64"] = {"value": None, "note": "failed: %r" % (exc,)}
-            oc.setDevice(dev, dtype)
-        if world == 1 and mode == "independent" and not args.no_cpu_baseline:
-            try:
-                out["cpu_baseline"], ores = cpu_baseline(w["kind"], d, args.n_grid, theta0, args.cpu_seeds or w["cpu_seeds"],
-                                                         max_workers=w["cpu_workers"])
-            except Exception as exc:          # the GPU measurement must not be lost to a host-side problem
-                out["cpu_baseline"], ores = dict(value=None, unit="trajectory outer-iterations/s", cores=0, kind="port",
-                                                 sample="failed: %r" % (exc,)), []
-            # parity of the HIP path with the oracle on the benchmark's own seeds (oracle in reference mode: its
-            # solve_ivp tolerance 1e-3 limits the agreement of the gradient to ~5e-3)
-            k = min(n_chk, len(ores))
-            out["parity_vs_oracle"] = None if k == 0 else {
-                "seeds": k,
-                "loss_rel_err_max": max(abs(chk_loss[i] - ores[i][0]) / abs(ores[i][0]) for i in range(k)),
-                "grad_rel_err_max": max(float(np.abs(chk_grad[i] - np.array(ores[i][1])).max() / np.abs(ores[i][1]).max())
-                                        for i in range(k)),
-                "note": None if args.config != "rocket" else
-                        "the rocket's cold starts end in DIFFERENT stationary points under different globalisations (DESIGN.md "
-                        "section 8): this compares the kernel's KKT point with the oracle's own, not a parity figure; the test tier "
-                        "certifies the kernel's answer with the oracle instead (tests/test_gpu_parity.py, 8 trajectories at n_grid 100)"}
+        if args.full:
+            from lfsd_amd import perf_model
+            n, m, p, nc = lib.n_state, lib.n_control, lib.n_auxvar, lib.n_const
+            dom = max(("oc_solve", "aux_riccati", "aux_forward"), key=lambda k: ktime[k])
+            nw, ni = L.taus.shape[1], len(d["interface"])
+            it_seed = seed_iterations(models, torch, w, args, L, dev) if seeded_f64(args, args.dtype, dom, args.warm_start) else None
+            useful_tflops, mfma_tflops, useful_flops, dom_dtype, valu_frac = kernel_model(perf_model, oc.model_spec(), args, args.dtype, aux_name, dom,
+                                                                                          ktime, float(it.mean()), units, B, args.warm_start, it_seed)
+            es = 4 if dom_dtype == "f32" else 8
+            abytes = B * algorithmic_bytes(dom, n, m, p, nc, args.n_grid, nw, ni, es)
+            achieved = abytes / (ktime[dom] * 1e-3) / 1e9
+            # PMC passes are separate rocprofv3 runs (tools/hbm_traffic.py, tools/issue_counters.py); the figures only apply
+            # to the workload they were collected on, so they are attached to the configuration's default command and null otherwise
+            tag = PROFILE_TAG if args.config == "quadrotor" else "%s_%s" % (PROFILE_TAG, args.config)
+            sources = {}
+
+            def profile(name, key=None):
+                """Counter figures that THIS run does not measure: read from a committed fold of separate rocprofv3 --pmc passes
+                of the same command, and named as such in the line (file + git blob hash of the file read, and the commit the
+                fold was collected at when the fold records it)."""
+                import hashlib
+                rel = "profiles/%s_%s.json" % (tag, name)
+                path = os.path.join(ROOT, rel)
+                if not (default_cmd and os.path.exists(path)):
+                    return {}
+                try:
+                    raw = open(path, "rb").read()
+                    js = json.loads(raw)
+                    sources[name] = {"file": rel, "git_blob": hashlib.sha1(b"blob %d\0" % len(raw) + raw).hexdigest(),
+                                     "collected_at_commit": js.get("collected_at_commit")}
+                    if key:
+                        return js.get(key) or {}
+                    return js.get(dom) or (js.get("oc_solve_wide", {}) if dom == "oc_solve" else {})      # (models solved on the wide mapping)
+                except Exception:
+                    return {}
+            traffic = profile("hbm_traffic").get("hbm_bytes_per_launch")
+            if traffic is not None and it_seed is not None:      # the fp32-seeded fp64 solve: both kernels of `oc_solve` move bytes
+                traffic += profile("hbm_traffic", "oc_solve_seed_f32").get("hbm_bytes_per_launch") or 0.0
+            issue = profile("issue_counters")
+            executed = issue.get("valu_flops_executed_per_launch")
+            if dom == "oc_solve":      # a two-launch wide solve (round 6): `oc_solve` is both launches, the folds keep the four-wavefront one apart
+                w4 = profile("hbm_traffic", "oc_solve_wide_w4").get("hbm_bytes_per_launch")
+                if traffic is not None and w4:
+                    traffic += w4
+                w4 = profile("issue_counters", "oc_solve_wide_w4").get("valu_flops_executed_per_launch")
+                if executed is not None and w4:
+                    executed += w4
+            peak = VALU_PEAK_TFLOPS[dom_dtype]
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "algorithmic_bytes_per_launch": abytes, "avg_launch_ms": ktime[dom],
+                               # the fraction that actually bounds this path: vector issue, not HBM
+                               "valu_useful_tflops": useful_tflops,
+                               "valu_frac": valu_frac, "valu_peak_tflops": peak, "kernel_dtype": dom_dtype,
+                               "seed_iters_mean_f32": it_seed,
+                               # what the vector pipe EXECUTED per launch by the counters (every enabled lane, redundant group-uniform
+                               # work included) at this run's launch time, and the modelled useful share of it
+                               "valu_executed_tflops": None if executed is None else executed / (ktime[dom] * 1e-3) / 1e12,
+                               "valu_useful_over_executed": None if executed is None else useful_flops / executed,
+                               "mfma_useful_tflops": mfma_tflops,
+                               "valu_issue_util": issue.get("valu_issue_util"),
+                               "valu_lane_util": issue.get("valu_lane_util"),
+                               "mfma_busy": issue.get("mfma_busy"),
+                               "source": sources or None,
+                               "note": "the per-trajectory recursions are latency/VALU-issue bound, not HBM bound: "
+                                       "algorithmic bytes are O(10 KB) per trajectory against O(10^7) FLOP of sequential "
+                                       "vector work per solve; valu_frac = useful VECTOR flops (perf_model.py, checked against the "
+                                       "counters in round 3) / the vector peak of the kernel's arithmetic (157.3 fp32, 78.6 fp64 TFLOP/s); "
+                                       "traffic, valu_issue_util, valu_lane_util (EXEC-enabled lanes per vector instruction) and "
+                                       "mfma_busy are NOT measured by this run: they come from the committed fold of separate rocprofv3 "
+                                       "--pmc passes of this command named in `source` (null when the run is not the configuration's "
+                                       "default command or no fold is committed for it); see DESIGN.md section 4"}
+            # the reference computes in fp64 throughout (CPDP.py:183, :329): the same workload at that precision, 5 steps after the
+            # timed region of the default fp32 headline line -- a reported figure beside `value`, which stays the fp32 rate
+            if (args.config == "quadrotor" and default_cmd and world == 1 and not args.no_f64_leg):
+                try:
+                    oc.setDevice(dev, torch.float64)
+                    L64, _, _ = build_learner(args, oc, d, lib, rank, world, mode, w)
+                    L64.count_unconverged = False
+                    e64, k64, _ = timed_steps(L64, 5, 1, sync, torch)
+                    st64 = L64._aux["stats"].double().cpu().numpy()
+                    u64 = {"aux_riccati": float(st64[:, 0].mean()) / args.n_grid, "aux_forward": float(st64[:, 2].mean()) / args.n_grid}
+                    d64 = max(("oc_solve", "aux_riccati", "aux_forward"), key=lambda k: k64[k])
+                    it64 = float(L64._sol["iters"].double().mean().item())
+                    a64 = argparse.Namespace(**dict(vars(args), dtype="f64"))
+                    seed64 = float(it.mean()) if seeded_f64(a64, "f64", d64, False) else None      # (the fp32 leg's own solves: same seeds, same rule)
+                    uf64, _, _, _, frac64 = kernel_model(perf_model, oc.model_spec(), a64, "f64", None, d64, k64, it64, u64, B, False, seed64)
+                    out["f64"] = {"value": B * 5 / e64, "unit": "trajectory outer-iterations/s", "steps": 5, "warmup": 1,
+                                  "ms_per_step": e64 / 5 * 1e3, "kernel_ms": {k: round(v, 3) for k, v in k64.items()},
+                                  "aux_units_per_interval": {k: round(v, 3) for k, v in u64.items()},
+                                  "oc_status_hist": np.bincount(L64._sol["status"].cpu().numpy(), minlength=5).tolist(),
+                                  "kernel": d64, "valu_useful_tflops": uf64, "valu_frac": frac64,
+                                  "oc_iters_mean": it64, "oc_seed_iters_mean_f32": seed64,
+                                  "note": "same seeds, every returned number and every convergence test in fp64 (the reference's precision); "
+                                          "the cold OC solve is seeded by the fp32 solve of the same problem (lfsd_capi.cpp, coc_solve_seeded; "
+                                          "oc_iters_mean counts both), so `oc_solve` is an fp32 and an fp64 kernel and valu_frac prices each "
+                                          "part at the vector peak of its arithmetic; model-only utilisation"}
+                    del L64
+                except Exception as exc:
+                    out["f64"] = {"value": None, "note": "failed: %r" % (exc,)}
+                oc.setDevice(dev, dtype)
+            if world == 1 and mode == "independent" and not args.no_cpu_baseline:
+                try:
+                    out["cpu_baseline"], ores = cpu_baseline(w["kind"], d, args.n_grid, theta0, args.cpu_seeds or w["cpu_seeds"],
+                                                             max_workers=w["cpu_workers"])
+                except Exception as exc:          # the GPU measurement must not be lost to a host-side problem
+                    out["cpu_baseline"], ores = dict(value=None, unit="trajectory outer-iterations/s", cores=0, kind="port",
+                                                     sample="failed: %r" % (exc,)), []
+                # parity of the HIP path with the oracle on the benchmark's own seeds (oracle in reference mode: its
+                # solve_ivp tolerance 1e-3 limits the agreement of the gradient to ~5e-3)
+                k = min(n_chk, len(ores))
+                out["parity_vs_oracle"] = None if k == 0 else {
+                    "seeds": k,
+                    "loss_rel_err_max": max(abs(chk_loss[i] - ores[i][0]) / abs(ores[i][0]) for i in range(k)),
+                    "grad_rel_err_max": max(float(np.abs(chk_grad[i] - np.array(ores[i][1])).max() / np.abs(ores[i][1]).max())
+                                            for i in range(k)),
+                    "note": None if args.config != "rocket" else
+                            "the rocket's cold starts end in DIFFERENT stationary points under different globalisations (DESIGN.md "
+                            "section 8): this compares the kernel's KKT point with the oracle's own, not a parity figure; the test tier "
+                            "certifies the kernel's answer with the oracle instead (tests/test_gpu_parity.py, 8 trajectories at n_grid 100)"}
         print(json.dumps(out), flush=True)
     if in_launcher:
         dist.barrier()

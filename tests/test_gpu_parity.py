@@ -918,7 +918,7 @@ def test_schedule_constants_on_held_out_workloads(name):
 
 @pytest.mark.parametrize("cfg,words", [("robotarm", ("configs[1]", "RobotArm")), ("rocket", ("configs[4]", "Rocket"))])
 def test_bench_config_lines_have_the_full_schema(cfg, words):
-    """`bench.py --config robotarm|rocket` (BASELINE configs[1] / configs[4]) as a fresh child at a small batch: one JSON line
+    """`bench.py --config robotarm|rocket --full` (BASELINE configs[1] / configs[4]) as a fresh child at a small batch: one JSON line
     with the headline's schema -- metric, value, roofline (with the kernel it names and its arithmetic), config.workload naming
     the configuration -- and a CPU leg from the oracle on the run's own seeds."""
     import json
@@ -926,7 +926,7 @@ def test_bench_config_lines_have_the_full_schema(cfg, words):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfg, "--batch", "64", "--steps", "2", "--warmup", "1",
-                        "--cpu-seeds", "4"], capture_output=True, text=True, timeout=900)
+                        "--cpu-seeds", "4", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -940,6 +940,42 @@ def test_bench_config_lines_have_the_full_schema(cfg, words):
     cb = o["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] and cb["value"] > 0, cb
     assert (cfg == "rocket") == ("f64 (auxiliary pass)" in o["dtype"])
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` (no --full) as a fresh child: exactly --steps timed steps, the headline fields, none of the --full legs;
+    --dump-outputs writes the last timed step's arrays in the run's precision, and their loss is the line's loss_mean.  A longer
+    window restarts the example's run and ends on the same, finite, outputs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "64", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    o = json.loads(lines[0])
+    assert o["steps"] == 3 and o["warmup"] == 1 and o["dtype"] == "f32" and o["higher_is_better"] is True
+    assert o["value"] > 0 and abs(o["value"] - 64 * 3 / (o["ms_per_step"] * 3e-3)) < 1e-6 * o["value"]
+    assert not {"roofline", "f64", "cpu_baseline", "parity_vs_oracle"} & set(o)
+    p = len(models.quadrotor()[2]["theta0"])
+    shapes = dict(loss=(64,), grad=(64, p), theta=(64, p), state_grid=(64, 51, 13), control_grid=(64, 51, 4))
+    got = {k: np.load(str(out_dir / (k + ".npy"))) for k in shapes}
+    assert sorted(os.listdir(str(out_dir))) == sorted(k + ".npy" for k in shapes)
+    for k, a in got.items():
+        assert a.shape == shapes[k] and a.dtype == np.float32, (k, a.shape, a.dtype)
+    assert abs(np.nanmean(got["loss"].astype(np.float64)) - o["config"]["loss_mean"]) <= 1e-6 * abs(o["config"]["loss_mean"])
+    # a window past the example's 50 outer iterations runs it again from the same seeds: 1 + 53 steps end where 1 + 3 do
+    assert o["config"]["outer_iters_per_run"] == 50
+    again = tmp_path / "again"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "64", "--steps", "53", "--warmup", "1",
+                        "--dump-outputs", str(again)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for k, a in got.items():
+        b = np.load(str(again / (k + ".npy")))
+        assert np.isfinite(b).all() and np.array_equal(a, b), k
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])

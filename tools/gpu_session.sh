@@ -16,8 +16,8 @@ o=json.load(open(sys.argv[1])); r=o.get('roofline',{})
 print(sys.argv[1].split('/')[-1], round(o['value']), o['ms_per_step'], o['config'].get('kernel_ms'), o['config'].get('oc_status_hist'), o['config'].get('aux_units_per_interval'), r.get('valu_frac'))" $1; }
 case $S in
 quick)
-  python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err; line $OUT/bench_f32.json
-  python3 bench.py --steps 10 --warmup 2 --dtype f64 --no-cpu-baseline > $OUT/bench_f64.json 2> $OUT/bench_f64.err; line $OUT/bench_f64.json
+  python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err; line $OUT/bench_f32.json
+  python3 bench.py --full --steps 10 --warmup 2 --dtype f64 --no-cpu-baseline > $OUT/bench_f64.json 2> $OUT/bench_f64.err; line $OUT/bench_f64.json
   rm -f $OUT/parity_floors.jsonl
   LFSD_PARITY_REPORT=$PWD/$OUT/parity_floors.jsonl timeout 1500 python3 -m pytest tests -m gpu -q -x -k "${K:-every_output_grid or bench_seeds or outer_iteration_12 or reference_shaped or time_varying or fp64_aux}" > $OUT/pytest_gpu.txt 2>&1
   tail -5 $OUT/pytest_gpu.txt ;;
@@ -44,11 +44,11 @@ final)        # the round's closing record: evidence sets (headline, fp64, the t
   bash tools/gpu_session.sh profile r06 > $OUT/profile.log 2>&1
   bash tools/gpu_session.sh f64 r06_f64 > $OUT/f64.log 2>&1
   bash tools/gpu_session.sh configs r06_c
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; line $OUT/bench_default.json
-  python3 bench.py --batch 32768 --steps 5 --warmup 1 --no-cpu-baseline --no-f64-leg > $OUT/bench_f32_32768.json 2> /dev/null; line $OUT/bench_f32_32768.json
-  python3 bench.py --batch 32768 --steps 3 --warmup 1 --dtype f64 --no-cpu-baseline > $OUT/bench_f64_32768.json 2> /dev/null; line $OUT/bench_f64_32768.json
-  python3 bench.py --mode shared --no-cpu-baseline > $OUT/bench_shared_one_gpu.json 2> /dev/null; line $OUT/bench_shared_one_gpu.json
-  NCCL_DEBUG=VERSION python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 1 --mode shared --backend nccl --no-cpu-baseline --no-f64-leg > $OUT/rccl_one_rank.txt 2>&1; tail -1 $OUT/rccl_one_rank.txt | head -c 300; echo
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; line $OUT/bench_default.json
+  python3 bench.py --full --batch 32768 --steps 5 --warmup 1 --no-cpu-baseline --no-f64-leg > $OUT/bench_f32_32768.json 2> /dev/null; line $OUT/bench_f32_32768.json
+  python3 bench.py --full --batch 32768 --steps 3 --warmup 1 --dtype f64 --no-cpu-baseline > $OUT/bench_f64_32768.json 2> /dev/null; line $OUT/bench_f64_32768.json
+  python3 bench.py --full --mode shared --no-cpu-baseline > $OUT/bench_shared_one_gpu.json 2> /dev/null; line $OUT/bench_shared_one_gpu.json
+  NCCL_DEBUG=VERSION python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 1 --mode shared --backend nccl --no-cpu-baseline --no-f64-leg > $OUT/rccl_one_rank.txt 2>&1; tail -1 $OUT/rccl_one_rank.txt | head -c 300; echo
   if [ -z "$NO_TIER" ]; then bash tools/gpu_session.sh tier ${TAG}_tier; fi ;;
 ms)           # round 5: the multiple-shooting phase of the wide kernel, product vs variants (tools/model_ab.py build robotarm noms -DLFSD_MS=0; ... rocket msnewton -DLFSD_MS_NEWTON=1)
   vp() { python3 -c "
@@ -56,10 +56,10 @@ import sys; sys.path.insert(0,'tools'); import oc_trace
 from lfsd_amd import models
 print(oc_trace.variant_path(models.ZOO[sys.argv[1]]()[0].model_spec(), sys.argv[2]))" $1 $2; }
   for c in ${CFGS:-robotarm rocket}; do
-    python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err; line $OUT/bench_$c.json
+    python3 bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err; line $OUT/bench_$c.json
   done
   for v in ${VARIANTS:-noms nohall}; do
-    python3 bench.py --config robotarm --steps 5 --warmup 1 --no-cpu-baseline --library $(vp robotarm $v) > $OUT/bench_robotarm_$v.json 2> $OUT/bench_robotarm_$v.err; line $OUT/bench_robotarm_$v.json
+    python3 bench.py --full --config robotarm --steps 5 --warmup 1 --no-cpu-baseline --library $(vp robotarm $v) > $OUT/bench_robotarm_$v.json 2> $OUT/bench_robotarm_$v.err; line $OUT/bench_robotarm_$v.json
   done
   python3 tools/config_steps.py robotarm 6 > $OUT/steps_robotarm.txt 2>&1; grep "^step" $OUT/steps_robotarm.txt
   LFSD_TOOL_LIBRARY=$(vp robotarm noms) python3 tools/config_steps.py robotarm 6 > $OUT/steps_robotarm_noms.txt 2>&1; grep "^step" $OUT/steps_robotarm_noms.txt
