@@ -295,7 +295,7 @@ template <class M, typename T, int G, int LAY> struct AuxCtx {
     T k[NX], acc[NX], zs[NX];
     if constexpr (aux_rk<T>() == 2) {
       // explicit midpoint rule: the Strang splitting around it is second order anyway, and in fp32 the rounding floor of
-      // the sweep hides the two orders the Richardson pair gains with RK4 (cpdp_common.h, LFSD_AUX_RK32)
+      // the sweep hides the two orders the Richardson pair gains with RK4 (cpdp_common.h, kAuxRk32)
       (void)n2; (void)acc;
       ric_rhs(z, n0, k);
 #pragma unroll
@@ -348,7 +348,8 @@ template <class M, typename T, int G, int LAY> struct AuxCtx {
   LFSD_DEV void fwd_prep(const T* zA, const T* zB, T s0, T ds, T hq) {
     T* ldsK = lds + Lay::LDS_KN;
     T* ldsP = lds + Lay::LDS_PSI;
-    LFSD_FWD_NODE_LOOP
+    // (outer per-node loops rolled: 5 % faster than unrolled, profiles/r01_tune_aux_occupancy.txt, r01_tune_compiler_flags.txt)
+#pragma unroll 1
     for (int r = 0; r < 3; ++r) {
       const T* L = node(2 * r);
       const T sr = s0 + T(2 * r) * ds;
@@ -455,7 +456,7 @@ template <class M, typename T, int G, int LAY> struct AuxCtx {
   // Three rounds for the five nodes: the fine lanes of a column take nodes 0, 1, 2, its coarse lanes nodes 3, 4 (and 4 again).
   LFSD_DEV void fwd_cols(const T* zA, const T* zB, T s0, T ds) {
     T* bc = lds + Lay::FWD_BC;
-    LFSD_FWD_NODE_LOOP
+#pragma unroll 1
     for (int rd = 0; rd < 3; ++rd) {
       const int nd = coarse ? (rd < 2 ? 3 + rd : 4) : rd;
       const T* L = node(nd);
@@ -608,8 +609,12 @@ template <class M, typename T, int G, int LAY> LFSD_DEV void aux_setup(AuxCtx<M,
 // (cpdp_common.h) is exactly that: an LDS-scoped release/acquire fence pair (s_waitcnt lgkmcnt(0) -- the DS queue of a
 // wavefront is in order) around a wave_barrier (a scheduling fence for the compiler, no instruction).  A port to multi-wave
 // workgroups would have to make `units` block-uniform first (as oc_solve_kernel does with its votes).
+// Occupancy, measured on MI355X (profiles/r01_tune_aux_occupancy.txt, r01_tune_compiler_flags.txt): compiled without clang's SLP
+// vectoriser the fp32 Riccati sweep runs two waves per SIMD -- the 2048 waves of the benchmark batch in one round instead of two,
+// 8.2 -> 5.7 ms once the coarse and the fine Richardson chain run in place with the other column parked in LDS (246 VGPRs).  The
+// forward sweep and fp64 stay at one wave per SIMD (256 + 256 registers): in place the forward sweep is 20 % slower.
 template <class M, typename T, int G>
-__global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux_riccati_kernel(AuxArgs<T> a) {
+__global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) aux_riccati_kernel(AuxArgs<T> a) {
   if (blockDim.x != 64) return;                   // one wavefront per workgroup: see the note on barriers above
   using Ctx = AuxCtx<M, T, G, 0>;
   using Lay = AuxLayout<M>;
@@ -683,7 +688,7 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
     // Step-size control INSIDE a stiff interval (round 6).  The uniform refinement below sizes every unit of an interval for its
     // stiffest point.  The interval before a heavy final cost is a transient: P starts at h_xx and decays like 1 / (1/P_0 + R tau) --
     // on the robot arm dgrid x rate falls from 2 000 to 1 inside that one interval, which took 500 of the sweep's 565 units (and
-    // 2.6 ms of a 15 ms learner step).  From LFSD_RIC_ADAPT units up the interval is integrated with steps of its own: every step is a
+    // 2.6 ms of a 15 ms learner step).  From kRicAdapt units up the interval is integrated with steps of its own: every step is a
     // Richardson pair as before, judged on ITS estimate against the same tolerances; a refused step is redone from its parked start
     // value with half the length; after a step whose estimate leaves an 8-fold margin the length doubles when the stiffness at the
     // NEW position allows it (dt x rate <= rate_max, evaluated on the coefficients the step has just staged at its far node).
@@ -693,7 +698,7 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
     // everywhere), its floors against the tight oracle were set on that, and it stays bit for bit what it was.
     bool adaptive_done = false;
     if constexpr (sizeof(T) == 4 && Lay::template ric_adaptive<G>()) {
-    if (a.rtol > T(0) && units >= (LFSD_RIC_ADAPT) && units_cap % units == 0) {
+    if (a.rtol > T(0) && units >= kRicAdapt && units_cap % units == 0) {
       adaptive_done = true;
       const int R = (int)units_cap;
       int stp = R / units, pos = R;
@@ -732,9 +737,6 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
         const bool fine_enough = (eP <= tolP && eW <= tolW) || !(t_finite(eP) && t_finite(eW));
         const T ratio = t_max(eP / t_max(tolP, T(1e-30)), eW / t_max(tolW, T(1e-30)));
         const bool no_gain = ratio_prev >= T(0) && ratio > T(0.5) * ratio_prev;      // (the halved step did not halve the estimate: next to a conjugate point)
-#if defined(LFSD_AUX_TRACE)
-        if (lane == 0 && slot < LFSD_AUX_TRACE) printf("ric traj %d k %d adaptive pos %d / %d step %d ratio %.3e\n", (int)slot, k, pos, R, stp, (double)ratio);
-#endif
         if (fine_enough || no_gain || stp == 1 || !valid) {
           if (!fine_enough) unmet = true;
           pos -= stp;
@@ -743,7 +745,7 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
           //  sized for the LOCAL stiffness each contribute what only the stiffest units of a uniform interval did: measured in fp64 -- robot
           //  arm n_grid 30, [P W] against the tight oracle -- 1e-8 uniform, 6.1e-7 with this margin, 7.0e-8 with a 256-fold one; in fp32
           //  the rounding floor of the sweep, 1e-5, hides the difference: [P W] 2.4e-6 / 8.7e-6 either way)
-          constexpr int MARGIN = LFSD_AUX_DOWN;
+          constexpr int MARGIN = kAuxDown;
           if (pos > 0 && eP * T(MARGIN) <= tolP && eW * T(MARGIN) <= tolW && pos % (2 * stp) == 0 && (long long)2 * stp * Sa <= R) {
             // (the stiffness where the NEXT step starts: node 4 of this step's staging sits exactly there)
             const int need = s.units_for(s.stiff_rate(z, s.node(4)), Sa, a.rate_max, refine_k);
@@ -805,14 +807,11 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
       const bool fine_enough = (eP <= tolP && eW <= tolW) || !(t_finite(eP) && t_finite(eW));
       const T ratio = t_max(eP / t_max(tolP, T(1e-30)), eW / t_max(tolW, T(1e-30)));
       const bool no_gain = ratio_prev >= T(0) && ratio > T(0.5) * ratio_prev;
-#if defined(LFSD_AUX_TRACE)
-      if (lane == 0 && slot < LFSD_AUX_TRACE) printf("ric traj %d k %d units %d ratio %.3e (P %.3e W %.3e) prior %d\n", (int)slot, k, units, (double)ratio, (double)(eP / t_max(tolP, T(1e-30))), (double)(eW / t_max(tolW, T(1e-30))), units_guess);
-#endif
       ratio_prev = ratio;
       if (fine_enough || no_gain || !valid || (long long)units * 2 > units_cap) {
         if (!fine_enough) ++n_unmet;       // refinement gave up (next to a conjugate point, or at the cap): reported, not hidden
         // next interval: start from this interval's units, or half of them when the estimate leaves room for it
-        units_hint = (eP * T(LFSD_AUX_DOWN) <= tolP && eW * T(LFSD_AUX_DOWN) <= tolW && units > Sa) ? units / 2 : units;
+        units_hint = (eP * T(kAuxDown) <= tolP && eW * T(kAuxDown) <= tolW && units > Sa) ? units / 2 : units;
         break;
       }
       units *= 2;
@@ -841,7 +840,7 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_RIC : 1)) aux
 }
 
 template <class M, typename T, int G>
-__global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_FWD : 1)) aux_forward_kernel(AuxArgs<T> a) {
+__global__ void __launch_bounds__(64, 1) aux_forward_kernel(AuxArgs<T> a) {
   if (blockDim.x != 64) return;                   // one wavefront per workgroup: see the note above aux_riccati_kernel
   using Ctx = AuxCtx<M, T, G, 1>;
   using Lay = AuxLayout<M, 1>;
@@ -990,9 +989,6 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_FWD : 1)) aux
         }
       }
       n_units += units;
-#if defined(LFSD_AUX_TRACE)
-      if (lane == 0 && slot < LFSD_AUX_TRACE) printf("fwd traj %d k %d ran units %d hc %.6e xa %.9e %.9e %.9e\n", (int)slot, k, units, (double)hc, (double)xa[0], (double)xa[1], (double)xa[2]);
-#endif
       if (!(a.rtol > T(0))) break;
       LFSD_WAVE_SYNC();
       ldsR[lane] = err_l; ldsR[G + lane] = scl_l;
@@ -1003,13 +999,10 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? LFSD_WAVES_FWD : 1)) aux
       const T tolX = T(3) * a.rtol * (sX + T(1e-2));       // dx/dtheta starts from zero: absolute floor 1e-2 * rtol
       const T ratio = eX / tolX;
       const bool no_gain = ratio_prev >= T(0) && ratio > T(0.5) * ratio_prev;
-#if defined(LFSD_AUX_TRACE)
-      if (lane == 0 && slot < LFSD_AUX_TRACE) printf("fwd traj %d k %d units %d ratio %.3e\n", (int)slot, k, units, (double)ratio);
-#endif
       ratio_prev = ratio;
       if (eX <= tolX || no_gain || !t_finite(eX) || (long long)units * 2 > units_cap) {
         if (!(eX <= tolX)) ++n_unmet;
-        units_hint = (eX * T(LFSD_AUX_DOWN) <= tolX && units > Sa) ? units / 2 : units;
+        units_hint = (eX * T(kAuxDown) <= tolX && units > Sa) ? units / 2 : units;
         break;
       }
       units *= 2;

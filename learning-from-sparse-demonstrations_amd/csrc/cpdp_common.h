@@ -1,4 +1,4 @@
-// Build switches, packed/MFMA primitives and the small dense helpers shared by every kernel.
+// Platform macros, build switches, tuning constants, packed/MFMA primitives and the small dense helpers shared by every kernel.
 // Part of the kernel sources collected by cpdp_kernels.h (include that header, not this one).
 #pragma once
 
@@ -7,8 +7,6 @@
 #if defined(LFSD_EMU)
 #include "simt_emu.h"
 #define LFSD_LAMBDA_INLINE
-#define LFSD_LAMBDA_BW
-#define LFSD_LAMBDA_RO
 #define LFSD_HD
 #else
 #include <hip/hip_runtime.h>
@@ -16,148 +14,22 @@
 #define LFSD_HD __host__ __device__
 // lambdas inside kernels must be inlined as well: a real call passes their by-reference captures through scratch
 #define LFSD_LAMBDA_INLINE __attribute__((always_inline))
-#define LFSD_LAMBDA_BW __attribute__((always_inline))
-#define LFSD_LAMBDA_RO __attribute__((always_inline))
 #endif
 
-// register budget: measured on MI355X (tools/tune.py) 1 wave/SIMD with all 512 VGPR+AGPR beats 2-3 waves with scratch spills
-#ifndef LFSD_WAVES_PER_SIMD
-#define LFSD_WAVES_PER_SIMD 1
-#endif
-#ifndef LFSD_WAVES_OC
-#define LFSD_WAVES_OC LFSD_WAVES_PER_SIMD
-#endif
-// aux kernels and occupancy, measured on MI355X.  Compiled with clang's SLP vectoriser (profiles/r01_tune_aux_occupancy.txt)
-// a second wave per SIMD never paid: held to 256 VGPRs the kernels spilled 0.5-1.3 KB/lane (Riccati 8.8 -> 9.0 ms, forward
-// 5.8 -> 11.1 ms).  Without SLP (profiles/r01_tune_compiler_flags.txt) the fp32 Riccati sweep needs 256 + 84 registers: with
-// the small column cache (LFSD_RIC_CACHE 2) it runs two waves per SIMD -- the 2048 waves of the benchmark batch in one
-// round instead of two, 8.2 -> 7.1 ms with 0.4 KB/lane of spills, and 5.7 ms with none (246 VGPRs) once the coarse and the
-// fine Richardson chain run in place with the other column parked in LDS.  The forward sweep stays at one wave per SIMD
-// (256 + 256 registers) and keeps its two chains as independent instruction streams: in place it is 20 % slower.
-// Error-controlled sub-stepping of the auxiliary sweeps: the next interval starts with HALF the units of this one when
-// this one's worst per-unit estimate is at most 1/LFSD_AUX_DOWN of its tolerance.  The estimate is the local error of
-// one split unit, O(h^3): measured on the headline workload it grows 7.4-8x when the units are halved
-// (profiles/r02_h_aux_units.txt), so an 8-fold margin predicts <= 0.93-1.0 of the tolerance after the halving.  (It was
-// 32 until that trace showed every trajectory integrating at 2-4x the units its tolerance asked for.  Measured on the
-// benchmark: 10 -> Riccati 2.28 ms, 8 -> 2.14 ms, 6 -> 2.28 ms again: below 8 the halved intervals fail their test and are
-// redone.)
-// Non-stiff part of a split unit of the auxiliary sweeps: 4 = classical RK4, 2 = explicit midpoint rule.  The Strang
-// splitting around it is second order either way; with RK4 the Richardson pair is (nearly) symmetric and the extrapolation
-// gains two orders, with the midpoint rule one -- at half the right-hand sides per unit.  Measured on MI355X
-// (profiles/r02_m_substeps_accuracy.txt, r02_m_*): in fp32 the sweeps' rounding floor (1e-5 relative) hides the
-// difference -- gradient error vs the tight oracle 1.2e-4 at rtol 1e-3 with both, Riccati 2.12 -> 1.47 ms, forward
-// 1.08 -> 0.91 ms on the benchmark -- so the fp32 kernels use the midpoint rule.  In fp64 (parity reference; the rocket's
-// auxiliary pass) RK4 stays: the midpoint rule cost the robot arm's large-sensitivity seeds a factor 3 in accuracy and
-// the rocket 12 % in time (more units).
-#ifndef LFSD_AUX_RK32
-#define LFSD_AUX_RK32 2
-#endif
-#ifndef LFSD_AUX_RK64
-#define LFSD_AUX_RK64 4
-#endif
-#ifndef LFSD_AUX_DOWN
-#define LFSD_AUX_DOWN 8
-#endif
-// Riccati sweep: intervals that need at least this many uniform units are integrated with step-size control inside the interval
-// (cpdp_aux.h, aux_riccati_kernel); a very large value switches it off
-#ifndef LFSD_RIC_ADAPT
-#define LFSD_RIC_ADAPT 16
-#endif
-// outer per-node loops of the once-per-unit preparation (ric_cols; fwd_prep, fwd_cols): rolled.  Measured: 6 % faster in
-// the Riccati sweep; the forward sweep preferred them unrolled (7 %) until it was compiled with the max-ILP scheduler,
-// since then rolled is 5 % faster there too (profiles/r01_tune_aux_occupancy.txt, r01_tune_compiler_flags.txt)
-#ifndef LFSD_RIC_NODE_LOOP
-#define LFSD_RIC_NODE_LOOP _Pragma("unroll 1")
-#endif
-#ifndef LFSD_FWD_NODE_LOOP
-#define LFSD_FWD_NODE_LOOP _Pragma("unroll 1")
-#endif
-// forward auxiliary sweep: operands of the stiff step / right-hand side fetched into registers with back-to-back LDS reads
-// (lds_fetch) before the sparse operators run -- bit 0: fp32 instantiation, bit 1: fp64.  Measured on MI355X (profiles/
-// r04_b): fp32 0.849 -> 0.625 ms (185 exposed LDS round trips per split unit become 7 batches); fp64 1.99 -> 2.30 ms (the
-// 96 + 13 doubles of a right-hand side do not fit beside the chain's state: scratch 144 -> 212 B/lane), so fp64 keeps
-// reading its operands where it uses them.
-// (LFSD_FWD_FETCH: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-#ifndef LFSD_WAVES_RIC
-#define LFSD_WAVES_RIC 2
-#endif
-#ifndef LFSD_WAVES_FWD
-#define LFSD_WAVES_FWD 1
-#endif
-
-// Levenberg shift ladder of the OC solve: factor up after a failed backward sweep / line search, factor down after an
-// accepted full step, and how many accepted full steps to hold before the shift returns to a level that has just failed.
-// Measured on BASELINE configs[1] (robot arm, 1024 seeds, tools/tune_arm.py, profiles/r01_tune_step_control.txt): with
-// x10 / x0.1 the accepted steps land on shifts up to 10x larger than necessary (over-damped) and every other backward
-// sweep fails; sqrt(10) rungs + a one-step hold cut the slowest seed from 87 to 65 iterations and the seeds that run
-// out of iterations at the step-1 parameters from 98 to 65 of 1024.  Handing over to the exact model as soon as
-// Gauss-Newton crawls (the oracle's rule, LFSD_GN_CRAWL) costs iterations here (27 -> 40 on average) and stays off.
-#ifndef LFSD_MU_UP
-#define LFSD_MU_UP 3.1623
-#endif
-#ifndef LFSD_MU_DOWN
-#define LFSD_MU_DOWN 0.31623
-#endif
-// generic backward sweep of a solve that runs Newton from its first iteration (exact_after == 0, the rocket): fraction of the
-// Levenberg shift a stage keeps when its Q_uu factorises with it (0: one shift for all stages).  Measured on the rocket learner
-// step with the coarse time grid: 0 -> 207 ms, 0.01 -> 191, 0.003 -> 149, 0.001 -> 150, 1e-4 -> 214 (profiles/r04_s_*).  Solves
-// that start with Gauss-Newton sweeps keep one shift: the robot arm's step went 28.4 -> 42.9 ms with a per-stage fraction.
-#ifndef LFSD_MU_STAGE_FRAC_NEWTON
-#define LFSD_MU_STAGE_FRAC_NEWTON 0.001
-#endif
-#ifndef LFSD_MU_HOLD
-#define LFSD_MU_HOLD 1
-#endif
-// (LFSD_GN_CRAWL: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// Levenberg shift of the Newton modes, measured on BASELINE configs[1] (robot arm, 1024 seeds, emulator + MI355X,
-// profiles/r02_arm_step_control.txt).  LFSD_REG_CONSISTENT: the value recursion continues with the SHIFTED Q_uu, i.e. the
-// sweep is the block LDL^T factorisation of (Lagrangian Hessian + mu I_u) -- the model the step actually minimises, and
-// what IPOPT's inertia correction delta_w does to the KKT matrix (CPDP.py:177-184).  With the unshifted Q_uu in the
-// recursion (Tassa's form) an indefinite Q_uu feeds -mu K^T K into V_xx, the sweep needs shifts 30x larger, and 64 of
-// 1024 seeds ran out of 100 iterations.  LFSD_HAM_SHIFT: shift the cheap Hamiltonian model as well instead of falling
-// back to Gauss-Newton (measured: no gain).
-// backward sweep: issue the loads of interval k-1 while interval k is processed (1; costs NX+1 + NX+NU registers), or load
-// each interval when the sweep gets there (0).  Round 2 measured no difference and kept 1 -- the compiler had sunk the
-// prefetch to its first use (LFSD_ISSUE_FENCE below); with the loads really issued ahead (r03_g_ab_prefetch_pin.txt)
-// oc_solve takes 2.65 ms against 2.59 ms without the prefetch: the 23 registers it holds through the stage cost more
-// accumulator-register traffic than the loads' latency does beside 7000 cycles of stage work.
-// the same look-ahead in the GENERIC backward sweep (OcSolver::backward: wide kernel, lock-step kernels without MFMA, fp64):
-// 1 = fp32 instantiations, 3 = fp64 too
-#ifndef LFSD_BW_PREFETCH_GEN
-#define LFSD_BW_PREFETCH_GEN 1
-#endif
-// stages of look-ahead of the wide kernel's costate sweep (0: load where used)
-#ifndef LFSD_CS_AHEAD
-#define LFSD_CS_AHEAD 3
-#endif
-// lean fp32 kernel of the 32-lane models: backward sweep on the matrix cores (1) or relayed on the vector pipe (0)
-#ifndef LFSD_MFMA_BACKWARD
-#define LFSD_MFMA_BACKWARD 1
-#endif
-// Gauss-Newton -> Hamiltonian (cheap Newton-like) stage-Hessian model: after the first accepted full step whose gain is
-// below this fraction of the new cost ("past the first big drops").  Measured on the benchmark: 0.9 changes nothing (6
-// iterations per solve either way), 3.0 -- switching right after the first step -- costs 2 % of the trajectories a 7th.
-#ifndef LFSD_HAM_SWITCH
-#define LFSD_HAM_SWITCH 0.3
-#endif
-// lean fp32 kernel of the 32-lane models: leave the structurally constant tangent columns of the model (Model::NZC, e.g.
-// the quadrotor's position) out of the roll-out, the workspace and the matrix products (1), or treat every column alike (0)
-#ifndef LFSD_STRUCT_COLS
-#define LFSD_STRUCT_COLS 1
-#endif
-// Mesh continuation of the lean fp32 OC kernel (cpdp_oc.h, oc_solve_kernel): one RK4 step per grid interval while full
-// steps gain more than LFSD_COARSE_SWITCH of the cost, then the reference's steps_per_grid.  LFSD_COARSE_START 0 switches it
-// off.  Measured on the benchmark (profiles/r03_d_ab_coarse_exit.txt, r03_e_ab_coarse_switch.txt), oc_solve per launch: off
-// 3.79 ms; switch at 3.0 (after the first step) 3.20; 0.3 (with the Gauss-Newton -> Hamiltonian hand-over) 2.93; 1e-2 2.94;
-// 1e-3 (one Newton-like step more on the coarse grid) 2.85; 1e-4 2.98; 0 (only when the coarse problem has converged) 3.66.
+// ---- build switches ----------------------------------------------------------------------------------------------------------
+// The schedules of the OC solve that the GPU tier and the emulator tests compare with a plain solve (lfsd_amd.runtime.
+// GPU_TIER_VARIANTS, tests/test_emu_kernels.py): each is set on the command line of a variant build.  Every other tuning choice
+// is a constant below.
+// Mesh continuation of the lean OC kernels (cpdp_oc.h, oc_solve_kernel): one RK4 step per grid interval while full steps gain
+// more than kCoarseSwitch of the cost, then the reference's steps_per_grid; 0 switches it off.  Measured on the benchmark
+// (profiles/r03_d_ab_coarse_exit.txt, r03_e_ab_coarse_switch.txt), oc_solve per launch: off 3.79 ms; switch at 3.0 (after the
+// first step) 3.20; 0.3 (with the Gauss-Newton -> Hamiltonian hand-over) 2.93; 1e-2 2.94; 1e-3 (one Newton-like step more on
+// the coarse grid) 2.85; 1e-4 2.98; 0 (only when the coarse problem has converged) 3.66.
 #ifndef LFSD_COARSE_START
 #define LFSD_COARSE_START 1
 #endif
-#ifndef LFSD_COARSE_SWITCH
-#define LFSD_COARSE_SWITCH 1e-3
-#endif
-// lean matrix-core kernels: level 0 of the mesh continuation merges LFSD_LEAN_TC control intervals (1: off) with LFSD_LEAN_TC_S RK4
-// steps per merged interval for the first LFSD_LEAN_TC_ITERS iterations of a cold start; never below LFSD_LEAN_TC_MIN intervals.
+// lean matrix-core kernels: level 0 of the mesh continuation merges LFSD_LEAN_TC control intervals (1: off) with kLeanTcS RK4
+// steps per merged interval for the first kLeanTcIters iterations of a cold start; never below kLeanTcMin intervals.
 // Measured on BOTH workloads of the benchmark (oc_solve per launch, 20 steps; profiles/r04_z_ab_lean_time_coarsening.txt) --
 // independent seeds (one start / goal, 4 096 parameter vectors: a homogeneous batch whose trajectories all walk the same path) |
 // shared parameters (4 096 random starts / goals / waypoints, the N > 1 workload: the launch lasts as long as its slowest path):
@@ -168,118 +40,33 @@
 #ifndef LFSD_LEAN_TC
 #define LFSD_LEAN_TC 2
 #endif
-#ifndef LFSD_LEAN_TC_S
-#define LFSD_LEAN_TC_S 1
-#endif
-#ifndef LFSD_LEAN_TC_ITERS
-#define LFSD_LEAN_TC_ITERS 3
-#endif
-#ifndef LFSD_LEAN_TC_MIN
-#define LFSD_LEAN_TC_MIN 12      // (round 5, held-out A/B: with 10 merged intervals -- n_grid 20 -- level 0 cost 14 % instead of saving; 13 and 15 save: profiles/r05_held_out_schedule_ab.jsonl)
-#endif
-// lean kernels: the convergence histories (last gradient norm, last predicted decrease) survive the step that leaves the coarse grid
-// when the coarse problem had converged (cpdp_oc.h); 0 = they always start over on the reference's grid
-#ifndef LFSD_EXIT_KEEP_HISTORY
-#define LFSD_EXIT_KEEP_HISTORY 2      // 1: only when the coarse problem had passed a convergence test; 2: also when the exit step predicted a decrease below the cost's resolution
-#endif
-// lean kernels: accepted steps after the transfer from level 0 during which a refused or shortened full step is answered by a line
-// search on the one-step-per-interval level instead of by leaving for the reference's grid (profiles/r04_bc_ab_grace_after_transfer.txt)
-#ifndef LFSD_LEAN_TC_GRACE
-#define LFSD_LEAN_TC_GRACE 2
-#endif
-// (a coarse phase for the wide kernel's models below 32 lanes was measured on the robot arm and removed: 21.2 -> 12.7 ms with the same
-//  minima on 1 023 of 1 024 seeds, but one seed follows the coarse discretisation to a minimum the reference's does not have:
-//  profiles/HISTORY.md, r04_ah_robotarm_coarse_phase_ab.txt)
-// wide kernel: the interval-parallel (multiple-shooting) iteration of OcWide::ms_* (cpdp_oc.h) -- the reference's own lifted
-// formulation, CPDP.py:136-172 -- for unbounded problems with at least LFSD_MS_MIN_GRID intervals; 0: single shooting only.
-// The phase hands over to the single-shooting iteration through a closed-loop roll-out, so every convergence test is unchanged.
+// wide kernel (one trajectory per wavefront): the interval-parallel (multiple-shooting) iteration of OcWide::ms_* (cpdp_oc.h) --
+// the reference's own lifted formulation, CPDP.py:136-172 -- for unbounded problems with at least kMsMinGrid intervals; 0: single
+// shooting only.  The phase hands over to the single-shooting iteration through a closed-loop roll-out, so every convergence test
+// is unchanged.
 #ifndef LFSD_MS
 #define LFSD_MS 1
 #endif
-#ifndef LFSD_MS_MIN_GRID
-#define LFSD_MS_MIN_GRID 40
-#endif
-// ... consecutive accepted SHORT steps (step length < 1) after which the phase ends on the current level (cpdp_oc.h)
-// wide kernel, fp32, models with at most 8 columns of [A B]: all columns of an interval's exact stage Hessian on one lane (1,
-// OcSolver::stage_hessian_all) or one (interval, column) item per lane (0)
-// (LFSD_HESS_ALL: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// (LFSD_LEAN_CTL_PREFETCH: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// ... shorter multiple-shooting steps: after a refused full step, at most LFSD_MS_HALF HALF steps in a row are tried before the
-// closed-loop roll-outs (0: none).  A trial costs 25 k clocks against a roll-out's 580 k.  Measured on the robot-arm learner
-// (1 024 seeds, MI355X, oc_solve of outer iterations 0 / 1 / 4 / 5 / 6 / 7; profiles/r05_o_*): none 12.5 / 11.1 / 17.8 / 7.5 / 7.9 / 8.2 ms,
-// one 10.9 / 10.2 / 8.7 / 7.2 / 5.5 / 5.2, two in a row 9.6 / 9.8 / 9.6 / 8.2 / 5.7 / 5.5.  (A full line search along the linear
-// direction -- built first, removed -- lets the gaps pile up: 1 % of the trajectories then need 45-50 iterations.)
-// (LFSD_MS_HALF: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// (LFSD_MS_JFEAS: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// (LFSD_MS_NEWTON: shipped as off since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// wide kernel (one trajectory per wavefront): smallest n_grid with a coarse phase
-#ifndef LFSD_COARSE_MIN_GRID
-#define LFSD_COARSE_MIN_GRID 40
-#endif
-// wide kernel: control intervals merged in the coarse phase (1: none, the coarse phase only takes one RK4 step per interval), and
-// the smallest coarse grid it may produce
+// wide kernel: control intervals merged in the coarse phase (1: none, the coarse phase only takes one RK4 step per interval)
 #ifndef LFSD_COARSE_TIME
 #define LFSD_COARSE_TIME 4
 #endif
-// wide kernel: 1 = between the merged-interval coarse level and the reference's grid, a level with one RK4 step per interval
-// (LFSD_COARSE_MID_LEVEL: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// RK4 steps per merged interval of that phase (0: as many as merged intervals, i.e. the step of one step per interval)
-#ifndef LFSD_COARSE_TIME_S
-#define LFSD_COARSE_TIME_S 2
-#endif
-#ifndef LFSD_COARSE_TIME_MIN
-#define LFSD_COARSE_TIME_MIN 20
-#endif
-// lfsd_coc_solve in fp64, lock-step mapping, 32-lane models, cold start: solve in fp32 first and start the fp64 kernel from those
-// controls with the Hamiltonian model (lfsd_capi.cpp, coc_solve_seeded).  Quadrotor headline in fp64: 9.8 -> see DESIGN section 3.1
-#ifndef LFSD_F64_SEED
-#define LFSD_F64_SEED 1
-#endif
-// wide kernel: when an accepted step that gains less than LFSD_COARSE_SWITCH of the cost ends the coarse phase (cpdp_oc.h)
-#ifndef LFSD_COARSE_EXIT_RULE
-#define LFSD_COARSE_EXIT_RULE 2
-#endif
-#ifndef LFSD_COARSE_EXIT_MU
-#define LFSD_COARSE_EXIT_MU 1e-2
-#endif
-// (LFSD_REG_CONSISTENT: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-
-// ---- fp64 OC kernels (round 3; profiles/r03_o_fp64_backward.txt, r03_q_fp64_live_park.txt) --------------------------------
-// fp64 lean OC kernel of the 32-lane models on 16-lane groups (four trajectories per wavefront); 0: 32-lane groups (round 2)
-// (LFSD_FP64_LIVE: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// ... with the between-stage values of its tangent RK4 step parked in LDS (OcSolver::rk4_step_parked)
-// (LFSD_FP64_PARK: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// ... and with the one-pass backward sweep of the structural-column layout (backward_sc, LDS-fed products) instead of two
-// passes of the generic sweep on 32-lane groups
-// (LFSD_FP64_SC: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// LFSD_FENCE64, bits: 1 = pin64 (row sums of the backward sweep's dense products are materialised where they are computed),
-// 2 = LFSD_SCHED_FENCE64 (a scheduling barrier per row), 4 = two row buffers (a row's LDS reads are issued while the previous
-// row is multiplied).  The pathology they remove: Q = [A B]^T Y is first used behind a branch; the compiler sank its FMAs
-// there, left the 221 LDS reads of their operands where they were, spilled every operand to scratch and reloaded it one at a
-// time -- 95 000 clocks for a stage that computes for 5 000, 66 % of oc_solve<double> (tools/oc_clock64.py).
-#ifndef LFSD_FENCE64
-#define LFSD_FENCE64 7
-#endif
-// ---- the generic backward sweep in fp32 (wide kernel, lock-step kernels without MFMA; profiles/r03_t_generic_backward.txt) --
-// wide kernel, models with at most 16 columns of [A B] and NX >= 8 (rocket): rows of the backward sweep's dense products
-// split over the four 16-lane quarters of the wavefront (OcSolver::backward, QS)
 // wide kernel, small fp32 models (at most 8 columns, NX * NXU <= 32): the backward sweep on LDS-staged operands, every lane running
-// the whole recursion (OcWide::backward_small)
+// the whole recursion (OcWide::backward_small, 1), or the generic sweep (0)
 #ifndef LFSD_BW_SMALL
 #define LFSD_BW_SMALL 1
 #endif
-// (LFSD_BW_QSPLIT: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
-// two row buffers for the dense products, fp32 instantiations with NX >= 8 (fp64: LFSD_FENCE64 & 4)
-// (LFSD_BW_ROWBUF32: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
+
+// ---- scheduling fences and LDS hand-overs -------------------------------------------------------------------------------------
 // LFSD_ROW_FENCE / LFSD_SCHED_FENCE64(T): the instruction scheduler moves nothing across this point (bounds the live ranges of
-// the fully unrolled contractions); LFSD_SCHED_FENCE: the same between the RK4 stages, off unless LFSD_USE_SCHED_FENCE is
-// defined.  No-ops in the emulator build.
+// the fully unrolled contractions); LFSD_SCHED_FENCE64 only in fp64 instantiations, one per row of the backward sweep's dense
+// products (see pin64 below).  No-ops in the emulator build.
 #if defined(LFSD_EMU)
 #define LFSD_ROW_FENCE()
 #define LFSD_SCHED_FENCE64(T)
 #else
 #define LFSD_ROW_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LFSD_SCHED_FENCE64(T) do { if constexpr (((LFSD_FENCE64) & 2) != 0 && sizeof(T) == 8) __builtin_amdgcn_sched_barrier(0); } while (0)
+#define LFSD_SCHED_FENCE64(T) do { if constexpr (sizeof(T) == 8) __builtin_amdgcn_sched_barrier(0); } while (0)
 #endif
 
 // LFSD_WAVE_SYNC: LDS hand-over between lanes of ONE wavefront (kernels whose workgroup is a single wavefront: the
@@ -304,21 +91,19 @@
 // global stores of the gains parks the wavefront until those stores are acknowledged by the L2 -- once per stage, ~1 600 of a
 // stage's 7 200 cycles by the phase clocks (profiles/r03_g_ab_prefetch_pin.txt, "K+Vupdate"), and it drains whatever was
 // prefetched for the next stage with it.  The gains are read by the NEXT roll-out, behind the block-wide votes of the main
-// loop (real __syncthreads); nothing inside the sweep reads them back.  LFSD_OC_LDS_SYNC 1: LDS-scoped fence there instead,
-// and the stage's loads are waited for at its top (cpdp_oc.h, backward_sc).  MEASURED (profiles/r04_j_ab_stage_sync.txt): the
+// loop (real __syncthreads); nothing inside the sweep reads them back.  So an LDS-scoped fence is used there instead, and the
+// stage's loads are waited for at its top (cpdp_oc.h, backward_sc).  MEASURED (profiles/r04_j_ab_stage_sync.txt): the
 // `s_waitcnt vmcnt(0)` behind the stores is gone from the stage's ISA and oc_solve takes exactly as long -- 2.587 ms against
-// 2.589 with the old syncs, 2.629 with the next stage's loads prefetched on top (LFSD_BW_PREFETCH 1): the stores are long
-// acknowledged when the wait is reached; the sweep is bound by issue, as round 3 concluded.  Kept: it is the narrower fence.
-// (LFSD_OC_LDS_SYNC: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
+// 2.589 with the old syncs, 2.629 with the next stage's loads prefetched on top: the stores are long acknowledged when the wait
+// is reached; the sweep is bound by issue, as round 3 concluded.  Kept: it is the narrower fence.
 #if defined(LFSD_EMU)
 #define LFSD_STAGE_SYNC() __syncthreads()
 #else
 #define LFSD_STAGE_SYNC() LFSD_WAVE_SYNC()
 #endif
 // ... the same inside a stage of the GENERIC backward sweep (wide kernel, lock-step kernels without MFMA): there the next
-// stage's global loads ARE issued a stage ahead (LFSD_BW_PREFETCH_GEN), and every __syncthreads() of the stage drained them.
+// stage's global loads ARE issued a stage ahead (fp32), and every __syncthreads() of the stage drained them.
 // Measured (profiles/r04_k_ab_generic_stage_sync.txt): rocket 107.8 / 107.5 ms, robot arm 17.8 / 17.7 ms with / without: nothing.
-// (LFSD_OC_LDS_SYNC_GEN: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
 #if defined(LFSD_EMU)
 #define LFSD_STAGE_SYNC_GEN() __syncthreads()
 #else
@@ -326,6 +111,58 @@
 #endif
 
 namespace lfsd {
+
+// ---- tuning constants (measured on MI355X; the alternatives are in the history) ---------------------------------------------
+// Levenberg shift ladder of the OC solve: sqrt(10) rungs up after a failed backward sweep / line search, down after an accepted
+// full step; x10 / x0.1 over-damps the accepted steps (profiles/r01_tune_step_control.txt)
+constexpr double kMuUp = 3.1623;
+constexpr double kMuDown = 0.31623;
+// accepted full steps to hold before the shift returns to a level that has just failed (slowest robot-arm seed 87 -> 65 iterations)
+constexpr int kMuHold = 1;
+// generic backward sweep of a Newton-from-start solve (exact_after == 0, the rocket): fraction of the shift a stage keeps when its
+// Q_uu factorises with it; rocket learner step 207 -> 150 ms (profiles/r04_s_rocket_time_coarsening_stage_shift_ab.txt)
+constexpr double kMuStageFracNewton = 0.001;
+// Gauss-Newton -> Hamiltonian stage-Hessian model after the first accepted full step that gains less than this fraction of the
+// new cost: 0.9 changes nothing, 3.0 (right after the first step) costs 2 % of the trajectories a 7th iteration
+constexpr double kHamSwitch = 0.3;
+
+// mesh continuation (LFSD_COARSE_START): the coarse phase ends after a full step that gains less than this fraction of the cost
+// (profiles/r03_e_ab_coarse_switch.txt)
+constexpr double kCoarseSwitch = 1e-3;
+// lean kernels, level 0 (LFSD_LEAN_TC): RK4 steps per merged interval, cold-start iterations on it, fewest merged intervals
+// (n_grid 20 -> 10 merged intervals cost 14 % instead of saving: profiles/r05_held_out_schedule_ab.jsonl)
+constexpr int kLeanTcS = 1;
+constexpr int kLeanTcIters = 3;
+constexpr int kLeanTcMin = 12;
+// lean kernels: accepted steps after the transfer from level 0 during which a refused or shortened full step is answered by a line
+// search on the one-step-per-interval level instead of by leaving for the reference's grid (profiles/r04_bc_ab_grace_after_transfer.txt)
+constexpr int kLeanTcGrace = 2;
+// wide kernel: smallest n_grid with a coarse phase, and with a multiple-shooting phase (LFSD_MS)
+constexpr int kCoarseMinGrid = 40;
+constexpr int kMsMinGrid = 40;
+// wide kernel, coarse phase with merged intervals (LFSD_COARSE_TIME): RK4 steps per merged interval (at most one per merged
+// interval; profiles/r04_af_rocket_coarse_rk4_steps_ab.txt) and the smallest coarse grid it may produce
+constexpr int kCoarseTimeS = 2;
+constexpr int kCoarseTimeMin = 20;
+// wide kernel: a step that gains less than kCoarseSwitch ends the coarse phase only when it was taken at a shift below this
+// (profiles/r04_u_rocket_coarse_exit_rule_ab.txt)
+constexpr double kCoarseExitMu = 1e-2;
+// wide kernel's costate sweep: stages of look-ahead of its column loads
+constexpr int kCsAhead = 3;
+// lfsd_coc_solve, automatic mapping: largest batch that runs the wide kernel where the lean MFMA kernel does not apply (below ~1500
+// trajectories most SIMDs would have no wavefront of the lock-step kernels: lfsd_capi.cpp, use_wide)
+constexpr int kWideMaxBatch = 1536;
+
+// Auxiliary sweeps: the non-stiff part of a split unit is the explicit midpoint rule in fp32 (the sweeps' rounding floor hides
+// the two orders RK4 gains: Riccati 2.12 -> 1.47 ms) and classical RK4 in fp64 (profiles/r02_m_substeps_accuracy.txt)
+constexpr int kAuxRk32 = 2;
+constexpr int kAuxRk64 = 4;
+// the next interval starts with HALF the units of this one when this one's worst per-unit estimate is at most 1/kAuxDown of its
+// tolerance: the O(h^3) estimate grows 7.4-8x when the units are halved (profiles/r02_h_aux_units.txt)
+constexpr int kAuxDown = 8;
+// Riccati sweep: intervals that need at least this many uniform units are integrated with step-size control inside the interval
+// (cpdp_aux.h, aux_riccati_kernel)
+constexpr int kRicAdapt = 16;
 
 // debug aid for the emulator build: start every kernel with NaN-filled LDS so that a read of
 // never-written shared memory cannot go unnoticed (tests build with -DLFSD_POISON_LDS)
@@ -546,14 +383,16 @@ template <int N, typename T> LFSD_DEV void lds_fetch(const T* src, T* dst) { lds
 // its FMAs sunk to that use by the compiler while its LDS reads stayed put (they cannot cross the barrier in between): all
 // 221 operands of Q = [A B]^T Y of the backward sweep were read, spilled to scratch and reloaded one by one -- 157 scratch
 // round trips per stage that miss the L2 (116 KB of scratch per wavefront), 95 000 cycles of a stage that computes for
-// about 5 000 (tools/oc_clock64.py, profiles/r03_o_fp64_backward.txt).  A pinned result keeps the FMAs with their reads.
-template <typename T> LFSD_DEV void pin64(T& x) { if constexpr (sizeof(T) == 8 && ((LFSD_FENCE64) & 1) != 0) pin(x); }
+// about 5 000 (profiles/r03_o_fp64_backward.txt).  A pinned result keeps the FMAs with their reads; with it the fp64 sweep
+// has a scheduling fence per row (LFSD_SCHED_FENCE64) and two row buffers, a row's LDS reads issued while the previous row is
+// multiplied (cpdp_oc.h, OcSolver::backward).
+template <typename T> LFSD_DEV void pin64(T& x) { if constexpr (sizeof(T) == 8) pin(x); }
 
 template <typename T> struct Eps;
 template <> struct Eps<float> { static LFSD_DEV float v() { return 1.1920929e-07f; } };
 template <> struct Eps<double> { static LFSD_DEV double v() { return 2.220446049250313e-16; } };
 
-template <typename T> LFSD_HD constexpr int aux_rk() { return sizeof(T) == 4 ? LFSD_AUX_RK32 : LFSD_AUX_RK64; }
+template <typename T> LFSD_HD constexpr int aux_rk() { return sizeof(T) == 4 ? kAuxRk32 : kAuxRk64; }
 
 template <typename T> LFSD_DEV T t_abs(T a) { return a < T(0) ? -a : a; }
 template <typename T> LFSD_DEV T t_max(T a, T b) { return a > b ? a : b; }
@@ -580,7 +419,6 @@ LFSD_DEV double t_rsqrt(double a) { return 1.0 / sqrt(a); }
 // products for |x| <= 100) + the two degree-7 / degree-8 minimax polynomials of cephes' sinf / cosf on [-pi/4, pi/4]; t_sin(a)
 // and t_cos(a) of the same argument share the reduction after inlining.  Measured against fp64 on 2^24 arguments in
 // [-100, 100] (trig_probe): see profiles/r04_l_trig_probe.txt.  Beyond |x| = 100, in fp64 and in the CPU emulator: the library.
-// (LFSD_FAST_TRIG: shipped as on since the round it was measured in; the switch was removed in round 6, the alternative is in the history)
 LFSD_DEV double t_sin(double a) { return sin(a); }
 LFSD_DEV double t_cos(double a) { return cos(a); }
 #if defined(LFSD_EMU)

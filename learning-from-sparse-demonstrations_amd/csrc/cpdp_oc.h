@@ -400,15 +400,8 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = x0[i];
     const int col = ZC_ + lane;          // lanes >= LIVE: col >= NXU, a zero tangent that is never stored
-#if defined(LFSD_OC_CLOCK) && !defined(LFSD_EMU)      // diagnostic build (tools/oc_clock64.py): clocks of control law | RK4 steps | stores, per roll-out
-    long long rck[3] = {0, 0, 0}, rck_t = clock64();
-#define LFSD_RCK(i) { const long long t_ = clock64(); rck[i] += t_ - rck_t; rck_t = t_; }
-#else
-#define LFSD_RCK(i)
-#endif
     for (int k = 0; k < N; ++k) {
       control(cur, k, x, alpha, gains, u);
-      LFSD_RCK(0)
       if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) xbp(nxt)[k * NX + i] = x[i];
@@ -426,7 +419,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       for (int s = 0; s < S; ++s) {
         rk4_step_parked<ZC_>(t, x, q, u, m, mq, du, qz);
       }
-      LFSD_RCK(1)
       J += q;
       if constexpr (SCL) {
         T* Ms = Mwp(nxt) + (long long)k * Lay::MS_ELEMS;
@@ -439,7 +431,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
           for (int z = 0; z < ZC_; ++z) Ms[(NX + 1) * Lay::LIVEP + z] = qz[z];
         }
-        LFSD_RCK(2)
         continue;
       }
       T* Mk = Mwp(nxt) + (long long)k * Lay::M_ELEMS;
@@ -462,10 +453,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       for (int i = 0; i < NX; ++i) xbp(nxt)[N * NX + i] = x[i];
     }
     J += M::final_cost(tk(N), x, e, c);
-#if defined(LFSD_OC_CLOCK) && !defined(LFSD_EMU)
-    if (threadIdx.x == 0 && blockIdx.x == 0) printf("rollout clock (wave 0): S %d intervals %d control %lld steps %lld stores %lld\n", S, N, rck[0], rck[1], rck[2]);
-#endif
-#undef LFSD_RCK
     return J;
   }
 
@@ -856,8 +843,8 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
     };
     // (the wide kernel and the lock-step kernels without a partner wavefront on their SIMD: one stage of look-ahead on the
     //  global loads of a stage -- rocket, wide fp32, n_grid 100: 128.8 -> 126.0 ms together with the costate sweep's,
-    //  profiles/r03_t_generic_backward.txt; fp64 lean quadrotor: 9.4 -> 11.9 ms, the registers are not there: off)
-    constexpr bool PFG = (LFSD_BW_PREFETCH_GEN) != 0 && (sizeof(T) == 4 || ((LFSD_BW_PREFETCH_GEN) & 2) != 0);
+    //  profiles/r03_t_generic_backward.txt; fp64 lean quadrotor: 9.4 -> 11.9 ms, the registers are not there: fp32 only)
+    constexpr bool PFG = sizeof(T) == 4;
     T m[NX], mq = T(0), mN[NX], mqN = T(0), xkN[NX], ukN[NU], dv[NX], dvN[NX];
     T hC[(EXACT && PFG) ? NXU : 1], hN[(EXACT && PFG) ? NXU : 1];
 #pragma unroll
@@ -947,7 +934,7 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
         for (int r = 0; r < NXU; ++r) Qcol[r] = quarter_sum(Qp[r]);
         (void)Y;
-      } else if constexpr (sizeof(T) == 8 ? ((LFSD_FENCE64) & 4) != 0 : NX >= 8) {
+      } else if constexpr (sizeof(T) == 8 || NX >= 8) {
         // a row's reads are issued while the previous row is multiplied (two row buffers, constant indices after the
         // unrolling).  fp64: with one buffer every row waited a full LDS round trip between the scheduling barriers; fp32
         // (wide kernel, lock-step kernels without MFMA): left to itself the compiler issued the 104 ds_read_b128 of a stage one
@@ -1019,15 +1006,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
             for (int a = 0; a < NU; ++a) hcol[(NX + a) * Lay::NXUP] = hu[a];
           }
         }
-#if defined(LFSD_TRACE_HCOL)
-        if (lane < NXU && blockIdx.x == 0 && threadIdx.x < G) {
-          printf("HCOL k %d lane %d x", k, lane); for (int i = 0; i < NX; ++i) printf(" %.17g", (double)xk[i]);
-          printf(" u"); for (int a = 0; a < NU; ++a) printf(" %.17g", (double)uk[a]);
-          printf(" l"); for (int i = 0; i < NX; ++i) printf(" %.17g", (double)lam[i]);
-          printf(" h"); for (int i = 0; i < NX; ++i) printf(" %.17g", (double)hx[i]); for (int a = 0; a < NU; ++a) printf(" %.17g", (double)hu[a]);
-          printf("\n");
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < NX; ++i) Qcol[i] += hx[i];
 #pragma unroll
@@ -1605,13 +1583,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
     for (int a = 0; a < NU; ++a) uk[a] = up[a];
   }
-  // diagnostic build (-DLFSD_BW_CLOCK, tools/bw_clock.py): shader clocks of the six phases of a stage, summed over a sweep
-#if defined(LFSD_BW_CLOCK) && !defined(LFSD_EMU)
-  long long bwc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define LFSD_BWC(i) { const long long t_ = clock64(); bwc[i] += t_ - bwc_t; bwc_t = t_; }
-#else
-#define LFSD_BWC(i)
-#endif
   LFSD_DEV bool backward_sc(int cur, int mode, T mu, bool live, T& gnorm, T& dV1, T& dV2, T& dmin) {
     static_assert(!Lay::sc_ok || (G == 16 && LIVE <= 16 && ZC <= NU && NX <= 16), "structural sweep: 16-lane groups");
     T* ldsV = lds + Lay::LDS_V;  T* ldsK = lds + Lay::LDS_K;
@@ -1660,9 +1631,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
     __syncthreads();
     T m[NX], mq = T(0), qzl = T(0);
     sc_load_stage(cur, N - 1, m, mq, qzl, xk, uk);
-#if defined(LFSD_BW_CLOCK) && !defined(LFSD_EMU)
-    long long bwc_t = clock64();
-#endif
     for (int k = N - 1; k >= 0; --k) {
       {
         // every global load of the stage lands HERE.  Loads and stores share one in-order counter on this hardware: the stage's
@@ -1725,7 +1693,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       }
       if constexpr (MM) {
         tile_transpose(acc);
-        LFSD_BWC(0)                                // loads issued, MFMA #1, stage Hessian column, transpose
 #pragma unroll
         for (int s_ = 0; s_ < NX; ++s_) yn[s_] = acc[s_ < ZC ? LX + s_ : s_ - ZC];
       }
@@ -1753,7 +1720,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       }
       if constexpr (MM) tile_transpose(acc);
       LFSD_STAGE_SYNC();                             // ldsYZ visible
-      LFSD_BWC(1)                                  // MFMA #2, gradient dot products, transpose
       // column of Q (natural row order) of this lane's V-role, control rows of its M-role
       T Qcol[NX], mu_rows[NU], Quxj[NU];
 #pragma unroll
@@ -1788,7 +1754,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
         gl_max = t_max(gl_max, t_abs(gl));
       }
       LFSD_STAGE_SYNC();
-      LFSD_BWC(2)                                  // gather of the constant states' columns, Q columns, Q_ux / Q_uu to LDS
       T Quu0[NU * NU], Lc[NU * NU], Qu[NU], kff[NU], Kj[NU], t1[NU];
 #pragma unroll
       for (int a = 0; a < NU; ++a) {
@@ -1816,7 +1781,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       T Vxj = Qg_v;
 #pragma unroll
       for (int a = 0; a < NU; ++a) { Vxj += Kj[a] * (qk[a] + Qu[a]); Vxj += Quxj[a] * kff[a]; }
-      LFSD_BWC(3)                                  // Q_uu from LDS, Cholesky, gains
       if (has_v) {
 #pragma unroll
         for (int a = 0; a < NU; ++a) ldsK[sv * NU + a] = Kj[a];
@@ -1848,7 +1812,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
         for (int i = 0; i < NX; ++i) lam_out[k * NX + i] = VXR ? lam[i] : ldsLam[i];
       }
-      LFSD_BWC(4)                                  // gains to LDS / HBM, V_xx update
       // symmetrise V_xx through LDS (the rank-1 feeds rely on row i == column i)
       if (has_v) {
 #pragma unroll
@@ -1869,7 +1832,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
         for (int i = 0; i < NX; ++i) ldsV[sv * NX + i] = vcol[i];
       }
-      LFSD_BWC(5)                                  // symmetrisation
       if (k > 0) sc_load_stage(cur, k - 1, m, mq, qzl, xk, uk);
     }
     ldsRed[lane] = gl_max;
@@ -1879,11 +1841,6 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
     for (int a = 0; a < NU; ++a) gnorm = t_max(gnorm, ldsRed[LX + a]);
     __syncthreads();
     if (!t_finite(gnorm) || !t_finite(dV1) || !t_finite(dV2)) ok = false;
-#if defined(LFSD_BW_CLOCK) && !defined(LFSD_EMU)
-    if (threadIdx.x == 0 && blockIdx.x == 0)
-      printf("bw clock (wave 0, one sweep of %d stages): mfma1+hess %lld  mfma2+dots %lld  gather+Qcol %lld  chol+gains %lld  K+Vupdate %lld  symm %lld\n",
-             N, bwc[0], bwc[1], bwc[2], bwc[3], bwc[4], bwc[5]);
-#endif
     return ok;
   }
   // costates and gradient norm without the value recursion (see costate_sweep_mf), structural layout
@@ -2149,35 +2106,29 @@ template <class M, typename T, bool EXACT, bool BND = false, int W = 1> struct O
       for (int i = 0; i < NX; ++i) lam_out[N * NX + i] = lam[i];
     }
     T gl_max = T(0);
-    // this lane's column of [A_k B_k; q_k], loaded LFSD_CS_AHEAD stages ahead of its use: the recursion itself is NX FMAs and
+    // this lane's column of [A_k B_k; q_k], loaded kCsAhead stages ahead of its use: the recursion itself is NX FMAs and
     // an LDS exchange per stage, a global load is ~1 500 clocks and nothing else runs on the SIMD
-    constexpr int AH = LFSD_CS_AHEAD;
-    T mc[AH > 0 ? AH : 1][NX + 1];
+    constexpr int AH = kCsAhead;
+    T mc[AH][NX + 1];
     auto load_col = [&](int k_, T* dst) LFSD_LAMBDA_INLINE {
       const T* Mk = Mwp(cur) + (long long)(k_ < 0 ? 0 : k_) * Lay::M_ELEMS + (lane < NXU ? lane : 0);
 #pragma unroll
       for (int i = 0; i <= NX; ++i) dst[i] = Mk[i * Lay::NXUP];
     };
-    if (AH > 0) {
 #pragma unroll
-      for (int j = 0; j < AH; ++j) load_col(N - 1 - j, mc[j]);
-    }
+    for (int j = 0; j < AH; ++j) load_col(N - 1 - j, mc[j]);
     for (int k = N - 1; k >= 0; --k) {
       T gl = T(0);
       T col[NX + 1];
-      if (AH > 0) {
 #pragma unroll
-        for (int i = 0; i <= NX; ++i) col[i] = mc[0][i];
+      for (int i = 0; i <= NX; ++i) col[i] = mc[0][i];
 #pragma unroll
-        for (int j = 0; j + 1 < AH; ++j) {
+      for (int j = 0; j + 1 < AH; ++j) {
 #pragma unroll
-          for (int i = 0; i <= NX; ++i) mc[j][i] = mc[j + 1][i];
-        }
-        load_col(k - AH, mc[AH - 1]);
-        LFSD_ISSUE_FENCE();
-      } else {
-        load_col(k, col);
+        for (int i = 0; i <= NX; ++i) mc[j][i] = mc[j + 1][i];
       }
+      load_col(k - AH, mc[AH - 1]);
+      LFSD_ISSUE_FENCE();
       if (lane < NXU) {
         gl = col[NX];
 #pragma unroll
@@ -2250,7 +2201,7 @@ template <class M, typename T, bool EXACT, bool BND = false, int W = 1> struct O
   //     instructions per stage.  (First version: the whole recursion on EVERY lane with the dense products packed two columns per
   //     instruction -- no exchange at all, 525 instructions per stage: oc_solve of the bench's five steps 11.05 ms against 10.38.)
   // Same recursion, same outputs (gains, feed-forward, costates, predicted decrease, failing pivot) as OcSolver::backward.
-  static constexpr bool SMALL_BW = EXACT && !BND && sizeof(T) == 4 && Lay::HALL && NX * NXU <= 32 && (LFSD_BW_SMALL) != 0;
+  static constexpr bool SMALL_BW = EXACT && !BND && sizeof(T) == 4 && Lay::HALL && NX * NXU <= 32 && LFSD_BW_SMALL != 0;
   static constexpr int BWS_STG = Lay::M_ELEMS + Lay::H_ELEMS + 2 * NX;      // words per stage
   LFSD_DEV bool small_bw_fits() const { return SMALL_BW && (N + 1) * BWS_STG <= Lay::template lds_ex_size<64, (int)sizeof(T)>(); }
   LFSD_DEV bool backward_small(int cur, int mode, T mu, T& gnorm, T& dV1, T& dV2, T& dmin) {
@@ -2829,8 +2780,9 @@ template <typename T> LFSD_DEV bool at_working_precision(int mode, T mu, T gnorm
 // trajectories instead of two; the backward sweep keeps its one-column-per-lane mapping on 32-lane groups and is run
 // in two passes.  The phases already meet in the per-trajectory scratch ([A B q], gains, nominal), so only the
 // few scalars of the step control cross between the mappings, through an LDS mailbox.
+// One wave per SIMD: with all 512 VGPR + AGPR it beats 2-3 waves with scratch spills (profiles/r01_tune_occupancy.txt).
 template <class M, typename T, int G, bool EXACT, bool PK = false>
-__global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a) {
+__global__ void __launch_bounds__(64, 1) oc_solve_kernel(OcArgs<T> a) {
   constexpr int GR = PK ? 16 : G;                 // lanes per trajectory of the roll-out / line-search mapping
   using Sol = OcSolver<M, T, GR, EXACT>;
   using SolB = OcSolver<M, T, G, EXACT>;          // backward-sweep mapping
@@ -2838,9 +2790,9 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
   constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NC = M::NC;
   constexpr int GPB = 64 / GR;
   // backward sweep of the packed kernel on the matrix cores (OcSolver::backward_mf) where the model fits 16-lane groups
-  constexpr bool MF = PK && (LFSD_MFMA_BACKWARD != 0) && sizeof(T) == 4 && NX <= 16 && NX + NU <= 17;
+  constexpr bool MF = PK && sizeof(T) == 4 && NX <= 16 && NX + NU <= 17;
   // ... without the structurally constant tangent columns of the model (OcSolver::backward_sc, rollout_sens_sc)
-  constexpr bool SC = MF && (LFSD_STRUCT_COLS != 0) && Lay::sc_ok;
+  constexpr bool SC = MF && Lay::sc_ok;
   constexpr int RS = EXACT ? Lay::template lds_elems<G>() : ((Lay::template lds_ex<G>() + 3) / 4) * 4;
   constexpr int MB = 12;                          // mailbox floats per trajectory
   static_assert(64 % G == 0 && G >= NX + NU, "lane group must hold one column of [A B] per lane");
@@ -2889,7 +2841,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
 
   // backward sweep of this lane's trajectory; `force`: also when the trajectory is no longer running (final refresh
   // of the costates).  Returns whether the sweep ran (PK skips a pass none of whose trajectories wants it).
-  auto do_backward = [&](int cur_, int mode_, T mu_, bool want_, T& gnorm_, T& dV1_, T& dV2_, T& dmin_, bool& ok_) LFSD_LAMBDA_BW -> bool {
+  auto do_backward = [&](int cur_, int mode_, T mu_, bool want_, T& gnorm_, T& dV1_, T& dV2_, T& dmin_, bool& ok_) LFSD_LAMBDA_INLINE -> bool {
     if constexpr (MF || SC64) {
       // all four trajectories of the wavefront sweep together on the matrix cores; a group that does not want the sweep
       // rides along without writing anything (the MFMAs need every lane)
@@ -2939,7 +2891,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
       return ran;
     }
   };
-  auto do_rollout = [&](int cur_, int nxt_, T alpha_, bool gains_) LFSD_LAMBDA_RO -> T {
+  auto do_rollout = [&](int cur_, int nxt_, T alpha_, bool gains_) LFSD_LAMBDA_INLINE -> T {
     if constexpr (SC) return s.rollout_sens_sc(cur_, nxt_, alpha_, gains_);
     else if constexpr (LV) return s.template rollout_sens_live<SC64>(cur_, nxt_, alpha_, gains_);
     else if constexpr (PK) return s.rollout_sens_pk(cur_, nxt_, alpha_, gains_);
@@ -2966,16 +2918,10 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
   }
   __syncthreads();
   int cur = 0;
-#if defined(LFSD_OC_CLOCK)
-  long long clk_bw = 0, clk_ro = 0, clk_ls = 0, clk_t0 = clock64();
-#define LFSD_CLK(acc, stmt) { const long long c0_ = clock64(); stmt; acc += clock64() - c0_; }
-#else
-#define LFSD_CLK(acc, stmt) { stmt; }
-#endif
   // Mesh continuation (lean fp32 kernel of the 32-lane models, round 3).  The first iterations of a cold start only have to
   // get near the optimum -- the zero-control roll-out of the quadrotor starts at J = 2.5e4 for an optimum of 10 -- and do
   // not need the reference's 4 RK4 steps per grid interval for that: while full steps keep gaining more than
-  // LFSD_COARSE_SWITCH of the cost, roll-outs and linearisations run with ONE RK4 step per interval (a quarter of the work
+  // kCoarseSwitch of the cost, roll-outs and linearisations run with ONE RK4 step per interval (a quarter of the work
   // of the phase that is 53 % of the kernel).  Then the nominal is rolled out and linearised once on the reference's
   // discretisation (`relin`, an iteration without a backward sweep) and the solve continues there: every convergence
   // test, every returned number belongs to the NLP of CPDP.py:110-175 with steps_per_grid sub-steps; the coarse phase only
@@ -2988,9 +2934,9 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
   bool relin = false;       // leave the coarse grid at the next iteration ...
   bool relin_hard = false;      // ... by a roll-out + linearisation of the nominal without a step (else: with the step)
   if (coarse) { s.S = 1; s.DT = s.dgrid; }
-  // Level 0 of the mesh continuation (round 4; the matrix-core kernels only): the first LFSD_LEAN_TC_ITERS iterations of a
+  // Level 0 of the mesh continuation (round 4; the matrix-core kernels only): the first kLeanTcIters iterations of a
   // workgroup whose trajectories are ALL cold also merge LFSD_LEAN_TC control intervals into one (n_grid / tc stages in the
-  // backward sweep, n_grid / tc * LFSD_LEAN_TC_S RK4 steps per roll-out), then the controls are prolongated -- each held over its
+  // backward sweep, n_grid / tc * kLeanTcS RK4 steps per roll-out), then the controls are prolongated -- each held over its
   // tc intervals -- and rolled out + linearised on the coarse level above (an iteration's roll-out without a step).  The
   // schedule is a fixed iteration count, so what a trajectory does never depends on its partners in the wavefront; a
   // trajectory that wants to leave the coarse phase earlier waits for it (the tests that set `relin` are deferred).
@@ -3005,9 +2951,9 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
     __syncthreads();
     const bool all_cold = vote[0] == 0;
     __syncthreads();
-    if (all_cold && N_full % (LFSD_LEAN_TC) == 0 && N_full / (LFSD_LEAN_TC) >= LFSD_LEAN_TC_MIN && a.max_iter > LFSD_LEAN_TC_ITERS + 6) {
+    if (all_cold && N_full % LFSD_LEAN_TC == 0 && N_full / LFSD_LEAN_TC >= kLeanTcMin && a.max_iter > kLeanTcIters + 6) {
       tc = LFSD_LEAN_TC;
-      s.N = N_full / tc; s.dgrid = dgrid_full * T(tc); s.S = LFSD_LEAN_TC_S; s.DT = s.dgrid / T(s.S);
+      s.N = N_full / tc; s.dgrid = dgrid_full * T(tc); s.S = kLeanTcS; s.DT = s.dgrid / T(s.S);
     }
   }
   T J = do_rollout(1, 0, T(0), false);
@@ -3046,7 +2992,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
   bool hess_ok = false;     // Hws holds the exact stage Hessians of nominal `cur`
   bool gn_crawl = false;    // Gauss-Newton is all that is left (Hamiltonian model failed) and its full steps gain < 1 %
   T mu_bad = T(-1);         // largest Levenberg shift that failed recently (<0: none)
-  int mu_hold = 0, mu_hold_need = LFSD_MU_HOLD;   // accepted full steps to wait before the shift returns to a level <= mu_bad
+  int mu_hold = 0, mu_hold_need = kMuHold;   // accepted full steps to wait before the shift returns to a level <= mu_bad
   // accepted steps after the transfer from level 0 during which a refused or shortened full step is NOT read as "past the big
   // drops, go to the reference's grid": there it only says that the level-0 model and this level disagree, and the line search
   // it asks for is four times cheaper here
@@ -3061,7 +3007,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
     if (!vote[0]) break;
     __syncthreads();
     if constexpr (TCL) {
-      if (tc > 1 && (it >= a.it_start + LFSD_LEAN_TC_ITERS || it + 5 >= a.max_iter)) {      // (uniform in the workgroup)
+      if (tc > 1 && (it >= a.it_start + kLeanTcIters || it + 5 >= a.max_iter)) {      // (uniform in the workgroup)
         // prolongation in place: control k of the finer level = control k / tc (chunks from the back: the source of element i is at
         // an index <= i, so no chunk overwrites the source of an earlier one)
         T* uc = s.ubp(cur);
@@ -3078,11 +3024,11 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
         if (relin && status == ST_RUNNING) { s.S = a.steps_per_grid; coarse = false; relin = false; } else { s.S = 1; }
         s.DT = s.dgrid / T(s.S);
         T Jt;
-        LFSD_CLK(clk_ro, Jt = do_rollout(cur, cur ^ 1, T(0), false));
+        Jt = do_rollout(cur, cur ^ 1, T(0), false);
         __syncthreads();
         cur ^= 1; J = Jt;
         need_bw = true; hess_ok = false; optimistic = true;
-        grace = coarse ? (LFSD_LEAN_TC_GRACE) : 0;
+        grace = coarse ? kLeanTcGrace : 0;
         g_last = T(-1); dec_last = T(1e30); g_flat = T(-1); J_ref = J; n_acc = 0;
         if (!t_finite(J) && status == ST_RUNNING) {
           if (coarse) { relin = true; relin_hard = true; }      // the reference's discretisation decides
@@ -3132,7 +3078,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
     bool bw_ok = false;
     s.reuse_hess = EXACT && mode == 2 && hess_ok;
     bool bw_ran = false;
-    LFSD_CLK(clk_bw, bw_ran = do_backward(cur, mode, mu, status == ST_RUNNING && !relin_now, gnorm, dV1, dV2, dmin, bw_ok));
+    bw_ran = do_backward(cur, mode, mu, status == ST_RUNNING && !relin_now, gnorm, dV1, dV2, dmin, bw_ok);
     if (bw_ran) { need_bw = false; hess_ok = EXACT && mode == 2; }
     bool try_step = false;
     if (relin_now) my_iters = it + 1 + it_off;
@@ -3146,7 +3092,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
           if (mu == T(0) && mode >= 1 && t_finite(dmin))
             mu = t_min(t_max(T(-2) * dmin, T(1e-4)), T(1e6));     // first shift: the size of the negative pivot
           else
-            mu = t_max(mu * T(LFSD_MU_UP), mode == 2 ? T(1e-4) : T(1e-6));
+            mu = t_max(mu * T(kMuUp), mode == 2 ? T(1e-4) : T(1e-6));
           if (mu > T(1e12)) status = ST_FAILED;
         }
       } else if (gnorm < a.tol * (T(1) + t_abs(J))) {
@@ -3175,7 +3121,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
     __syncthreads();
     const bool any_ls = vote[1] != 0;
     __syncthreads();
-    if (any_ls) LFSD_CLK(clk_ls, ia = s.linesearch(cur, J, dV1, dV2, alpha, Jmin, flat_full));
+    if (any_ls) ia = s.linesearch(cur, J, dV1, dV2, alpha, Jmin, flat_full);
     bool accept = false;
     if (ls_try) {
       if (ia >= 0) {
@@ -3191,12 +3137,9 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
         status = ST_STALLED;      // no step length gains more than rounding noise
       } else {                    // (exact model far from the optimum: indefinite direction -> larger shift)
         mu_bad = mu; mu_hold = 0;
-        mu = t_max(mu * T(LFSD_MU_UP), mode == 2 ? T(1e-4) : T(1e-6));
+        mu = t_max(mu * T(kMuUp), mode == 2 ? T(1e-4) : T(1e-6));
       }
     }
-#if defined(LFSD_TRACE)
-    if (s.lane == 0 && slot == 0) printf("it %d st %d mode %d bw_ok %d g %.6e J %.12e opt %d ia %d alpha %g accept %d mu %g dV1 %.4e dV2 %.4e Jmin %.12e flat %d\n", it, status, mode, (int)bw_ok, (double)gnorm, (double)J, (int)opt_try, ia, (double)alpha, (int)accept, (double)mu, (double)dV1, (double)dV2, (double)Jmin, (int)flat_full);
-#endif
     const bool roll = accept || opt_try;
     if (threadIdx.x == 0) vote[1] = 0;
     __syncthreads();
@@ -3205,7 +3148,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
     if (vote[1]) {
       T Jn;
       if (relin_now || (fine_step && opt_try)) { s.S = a.steps_per_grid; s.DT = s.dgrid / T(s.S); coarse = false; }
-      LFSD_CLK(clk_ro, Jn = do_rollout(cur, cur ^ 1, opt_try ? T(1) : (accept ? alpha : T(0)), roll));
+      Jn = do_rollout(cur, cur ^ 1, opt_try ? T(1) : (accept ? alpha : T(0)), roll);
       if (relin_now) {
         // the same controls on the reference's discretisation: new nominal, new cost, fresh linearisation; the histories of
         // the convergence tests start over
@@ -3235,7 +3178,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
         }
       }
       if (accept) {
-        if (coarse && ((ia != 0 && grace == 0) || (J - Jn) < T(LFSD_COARSE_SWITCH) * t_abs(Jn))) { relin = true; if (ia != 0) relin_hard = true; }      // past the first big drops
+        if (coarse && ((ia != 0 && grace == 0) || (J - Jn) < T(kCoarseSwitch) * t_abs(Jn))) { relin = true; if (ia != 0) relin_hard = true; }      // past the first big drops
         if (grace > 0) --grace;
         cur ^= 1;
         g_last = gnorm; dec_last = (mode >= 1 && mu == T(0)) ? -(dV1 + dV2) : T(1e30);
@@ -3248,7 +3191,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
         // (... or, the same situation reached by the gain rule: the step that left the coarse grid was a Newton-like step without a
         //  shift that itself predicted a decrease below the resolution of the cost)
         const bool below_res = mode >= 1 && mu == T(0) && -(dV1 + dV2) <= T(2) * Eps<T>::v() * t_abs(J);
-        if (fine_step && !((LFSD_EXIT_KEEP_HISTORY) != 0 && (conv_coarse || ((LFSD_EXIT_KEEP_HISTORY) > 1 && below_res)))) { g_last = T(-1); dec_last = T(1e30); }
+        if (fine_step && !(conv_coarse || below_res)) { g_last = T(-1); dec_last = T(1e30); }
         if (fine_step) { g_flat = T(-1); J_ref = Jn; n_acc = 0; }
         need_bw = true;
         hess_ok = false;
@@ -3257,13 +3200,13 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
           // relax the shift after a full step -- but not straight back to a level that has just failed: hold for
           // mu_hold_need accepted steps first, and twice as long after every failed return (a shift that bounces
           // between a failing and a working level wastes every other backward sweep)
-          const T mu_next = (mu > T(1e-8)) ? mu * T(LFSD_MU_DOWN) : T(0);
+          const T mu_next = (mu > T(1e-8)) ? mu * T(kMuDown) : T(0);
           if (mu > T(0) && mu_bad >= T(0) && mu_next <= mu_bad && mu_hold < mu_hold_need) {
             ++mu_hold;
           } else {
             mu = mu_next; mu_hold = 0;
           }
-          if (mode == 0 && ham_ok && (J - Jn) < T(LFSD_HAM_SWITCH) * t_abs(Jn)) mode = 1;      // past the first big drops: Newton-like
+          if (mode == 0 && ham_ok && (J - Jn) < T(kHamSwitch) * t_abs(Jn)) mode = 1;      // past the first big drops: Newton-like
           else if (mode == 0 && !ham_ok && (J - Jn) < T(1e-2) * t_abs(Jn)) gn_crawl = true;
         }
         J = Jn;
@@ -3281,12 +3224,7 @@ __global__ void __launch_bounds__(64, LFSD_WAVES_OC) oc_solve_kernel(OcArgs<T> a
   __syncthreads();
   if (need_bw) vote[0] = 1;
   __syncthreads();
-  { T dmin = T(0); bool okf = false; if (vote[0]) LFSD_CLK(clk_bw, do_backward(cur, 0, T(0), need_bw, gnorm, dV1, dV2, dmin, okf)); }   // refresh costates on the final nominal
-#if defined(LFSD_OC_CLOCK)
-  if (threadIdx.x == 0 && blockIdx.x < LFSD_OC_CLOCK)
-    printf("oc clock wave %d: iterations %d total %lld backward %lld rollout %lld linesearch %lld (shader clocks)\n", (int)blockIdx.x, it, clock64() - clk_t0, clk_bw, clk_ro, clk_ls);
-#endif
-#undef LFSD_CLK
+  { T dmin = T(0); bool okf = false; if (vote[0]) do_backward(cur, 0, T(0), need_bw, gnorm, dV1, dV2, dmin, okf); }   // refresh costates on the final nominal
   __syncthreads();
   if (valid) {
     T* xo = a.state_grid + traj * (N + 1) * NX;
@@ -3391,7 +3329,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
   // then leaves gaps as large as the step closes, the line search settles on steps of 1/4, and the phase needs as many or more
   // iterations than the closed-loop nonlinear roll-out while saving only the roll-outs' 20 % of an iteration (measured:
   // DESIGN.md).
-  const bool ms_on = !BND && (LFSD_MS) != 0 && a.n_grid >= (LFSD_MS_MIN_GRID) && a.max_iter > 8 && a.exact_after != 0;
+  const bool ms_on = !BND && LFSD_MS != 0 && a.n_grid >= kMsMinGrid && a.max_iter > 8 && a.exact_after != 0;
   bool ms = ms_on, ms_check = false, ms_floor = false;
   int n_acc_need = 4, n_ms = 0, n_half = 0;
   T g1c = T(0), g2c = T(0), gmc = T(0);      // l1 norm, sum of squares and largest entry of the gaps of the current iterate (0: a roll-out)
@@ -3402,14 +3340,6 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
   int status = ST_RUNNING, it = 0;
   T gnorm = T(0), dV1 = T(0), dV2 = T(0), g_flat = T(-1), g_last = T(-1), dec_last = T(1e30), J_ref = T(0), mu_bad = T(-1);
   int n_acc = 0, mu_hold = 0;
-#if defined(LFSD_OC_CLOCK)      // diagnostic build (tools/wide_clock.py): shader clocks of the phases of the slowest solves
-  long long wck[7] = {0, 0, 0, 0, 0, 0, 0}, wck_exit = 0;
-  int wck_it_exit = -1;
-  const long long wck_t0 = clock64();
-#define LFSD_WCK(i, stmt) { const long long c0_ = clock64(); stmt; wck[i] += clock64() - c0_; }
-#else
-#define LFSD_WCK(i, stmt) { stmt; }
-#endif
   if (!resuming) {
   // initial guess into buffer 1 (the reference's w0: zero, or the midpoint of finite control bounds, CPDP.py:153), rolled out
   // without gains into buffer 0, linearised
@@ -3434,14 +3364,14 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
     for (int l = 0; l < 64; ++l) warm = warm || !(ldsRed[l] == T(0));
   }
   __syncthreads();
-  coarse = CSW && a.steps_per_grid > 1 && !warm && a.max_iter > 8 && a.n_grid >= LFSD_COARSE_MIN_GRID;
+  coarse = CSW && a.steps_per_grid > 1 && !warm && a.max_iter > 8 && a.n_grid >= kCoarseMinGrid;
   if (coarse) {
-    constexpr int TC0 = (NX + (NU > NP ? NU : NP) > 16) ? (LFSD_COARSE_TIME) : 1;      // (the small models: one RK4 step per interval only, measured)
+    constexpr int TC0 = (NX + (NU > NP ? NU : NP) > 16) ? LFSD_COARSE_TIME : 1;      // (the small models: one RK4 step per interval only, measured)
     for (int f = TC0; f > 1; f /= 2) {
-      if (f <= Lay::SMAX && N_full % f == 0 && N_full / f >= LFSD_COARSE_TIME_MIN) { tc = f; break; }
+      if (f <= Lay::SMAX && N_full % f == 0 && N_full / f >= kCoarseTimeMin) { tc = f; break; }
     }
     s.N = N_full / tc; s.dgrid = dgrid_full * T(tc);
-    s.S = ((LFSD_COARSE_TIME_S) > 0 && (LFSD_COARSE_TIME_S) < tc) ? (LFSD_COARSE_TIME_S) : tc; s.DT = s.dgrid / T(s.S);
+    s.S = kCoarseTimeS < tc ? kCoarseTimeS : tc; s.DT = s.dgrid / T(s.S);
   }
   J = s.rollout_alphas(1, false, alpha_l);             // (every lane rolls the same controls out; lane 0's copy is adopted)
   ldsRed[s.lane] = J;
@@ -3476,7 +3406,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
     s.gap = has_gap ? s.gapp(cur) : nullptr;
     status = ST_RUNNING;
   }
-  const int mu_hold_need = LFSD_MU_HOLD;
+  const int mu_hold_need = kMuHold;
   bool suspended = false;
 #if defined(LFSD_TEST_REFUSE_GAPPED)
   int n_test_refused = 0;
@@ -3504,9 +3434,6 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
       //  interval -- the lean kernels' coarse level -- and leaves that one by the same rules)
       const bool to_mid = coarse && tc > 1 && a.steps_per_grid > 1 && it + 8 < a.max_iter;
       coarse = to_mid; relin = false;
-#if defined(LFSD_OC_CLOCK)
-      if (!to_mid) { wck_exit = clock64() - wck_t0; wck_it_exit = it; }
-#endif
       if (tc > 1) {
         // prolongation: control k of the reference grid = control k / tc of the coarse one (in place: sources into registers first)
         // (chunks of 64 from the back: the source of element i is at an index <= i, so no chunk overwrites a later chunk's source)
@@ -3541,23 +3468,23 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
       // costate sweep alone (no gains, no Hessians)
       ms_check = false;
       T gn;
-      LFSD_WCK(2, gn = s.costate_sweep(cur));
+      gn = s.costate_sweep(cur);
       costates_ok = true;
       if (gn < a.tol * (T(1) + t_abs(J))) { gnorm = gn; if (coarse) { relin = true; continue; } status = ST_CONVERGED; break; }
     }
     if (EXACT && a.exact_after >= 0 && mode < 2 && (it >= a.exact_after || gn_crawl)) mode = 2;
     if (EXACT && mode == 2 && !hess_ok) {
-      LFSD_WCK(2, s.costate_sweep(cur));
-      LFSD_WCK(3, s.hessians_parallel(cur));
+      s.costate_sweep(cur);
+      s.hessians_parallel(cur);
       hess_ok = true;
     }
     s.reuse_hess = EXACT && mode == 2;
     T dmin = T(0);
     bool bw_ok;
     if constexpr (std::remove_reference<decltype(s)>::type::SMALL_BW) {
-      LFSD_WCK(4, bw_ok = s.small_bw_fits() ? s.backward_small(cur, mode, mu, gnorm, dV1, dV2, dmin) : s.backward(cur, mode, mu, gnorm, dV1, dV2, dmin));
+      bw_ok = s.small_bw_fits() ? s.backward_small(cur, mode, mu, gnorm, dV1, dV2, dmin) : s.backward(cur, mode, mu, gnorm, dV1, dV2, dmin);
     } else {
-      LFSD_WCK(4, bw_ok = s.backward(cur, mode, mu, gnorm, dV1, dV2, dmin));
+      bw_ok = s.backward(cur, mode, mu, gnorm, dV1, dV2, dmin);
     }
     costates_ok = bw_ok;                              // (a sweep that failed stopped at the failing stage)
     if (!bw_ok) {
@@ -3565,7 +3492,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
       else {
         mu_bad = mu; mu_hold = 0;
         if (mu == T(0) && mode >= 1 && t_finite(dmin)) mu = t_min(t_max(T(-2) * dmin, T(1e-4)), T(1e6));
-        else mu = t_max(mu * T(LFSD_MU_UP), mode == 2 ? T(1e-4) : T(1e-6));
+        else mu = t_max(mu * T(kMuUp), mode == 2 ? T(1e-4) : T(1e-6));
         if (mu > T(1e12)) status = ST_FAILED;
       }
       continue;
@@ -3590,7 +3517,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
       }
       if (!close_now) {
         T lamd0, lamabs0, Dlin;
-        LFSD_WCK(5, Dlin = s.ms_forward(cur, lamd0, lamabs0));
+        Dlin = s.ms_forward(cur, lamd0, lamabs0);
         // Merit function of the multiple-shooting step: the augmented Lagrangian of the lifted NLP with the costates of THIS iterate,
         //     m = J + lambda^T d + rho/2 |d|^2,   rho = max(|lambda|_inf, 1)
         // (lambda^T d is what closing the gaps costs to first order).  The full Newton step closes the linearised gaps entirely:
@@ -3614,7 +3541,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
           }
         } else {
           T Jt, lat, ldt, g2t, g1t, gmt;
-          LFSD_WCK(6, s.ms_trial(cur, cur ^ 1, T(1), Jt, lat, ldt, g2t, g1t, gmt));
+          s.ms_trial(cur, cur ^ 1, T(1), Jt, lat, ldt, g2t, g1t, gmt);
           T phit = Jt + ldt + T(0.5) * rho * g2t;
           const T flat = T(8) * epsT * t_abs(phi0);
           bool accept = t_finite(phit) && t_finite(g1t) && (phi0 - phit) >= T(1e-4) * pred_ms - flat && phit < phi0 &&
@@ -3623,15 +3550,12 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
           if (!accept && n_half < 1) {
             // ONE shorter step along the same linear direction before the closed-loop roll-outs (an item of 25 k clocks against
             // 580 k): half the Newton step, same tests; it leaves half of the old gaps, so no second one follows it directly
-            LFSD_WCK(6, s.ms_trial(cur, cur ^ 1, T(0.5), Jt, lat, ldt, g2t, g1t, gmt));
+            s.ms_trial(cur, cur ^ 1, T(0.5), Jt, lat, ldt, g2t, g1t, gmt);
             phit = Jt + ldt + T(0.5) * rho * g2t;
             accept = t_finite(phit) && t_finite(g1t) && (phi0 - phit) >= T(0.5e-4) * pred_ms - flat && phit < phi0 &&
                      Jt <= J_feas + T(8) * epsT * t_abs(J_feas);
             half = accept;
           }
-#if defined(LFSD_TRACE)
-          if (s.lane == 0 && traj == 0) printf("wide ms it %d mode %d g %.6e J %.12e gap1 %.4e gapmax %.3e lam %.3e rho %.3e phi0 %.10e pred %.4e accept %d mu %g -> J %.12e gap1 %.4e phi %.10e\n", it, mode, (double)gnorm, (double)J, (double)g1c, (double)gmc, (double)lam_mx, (double)rho, (double)phi0, (double)pred_ms, (int)accept, (double)mu, (double)Jt, (double)g1t, (double)phit);
-#endif
           if (accept) {
             const T mu_taken = mu;
             const T gain = phi0 - phit;
@@ -3641,12 +3565,12 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
             // (no hold on the way down after a multiple-shooting step: a shift that turns out too small costs one backward sweep on
             //  cached Hessians, a held rung costs a whole iteration -- 128 seeds, emulator: mean 21.1 -> 19.8, slowest 33 -> 30
             //  iterations; dropping by 10 after steps that gain half their prediction: one seed at 52)
-            if (!half) { mu = (mu > T(1e-8)) ? mu * T(LFSD_MU_DOWN) : T(0); mu_hold = 0; }
+            if (!half) { mu = (mu > T(1e-8)) ? mu * T(kMuDown) : T(0); mu_hold = 0; }
             n_half = half ? n_half + 1 : 0;
-            if (mode == 0 && ham_ok && gain < T(LFSD_HAM_SWITCH) * t_abs(Jt)) mode = 1;
+            if (mode == 0 && ham_ok && gain < T(kHamSwitch) * t_abs(Jt)) mode = 1;
             else if (mode == 0 && !ham_ok && gain < T(1e-2) * t_abs(Jt)) gn_crawl = true;
-            if (coarse && gain < T(LFSD_COARSE_SWITCH) * t_abs(Jt)) {
-              if ((LFSD_COARSE_EXIT_RULE) <= 1 || ((LFSD_COARSE_EXIT_RULE) == 2 && mu_taken <= T(LFSD_COARSE_EXIT_MU))) relin = true;
+            if (coarse && gain < T(kCoarseSwitch) * t_abs(Jt)) {
+              if (mu_taken <= T(kCoarseExitMu)) relin = true;
             }
             J = Jt; g1c = g1t; g2c = g2t; gmc = gmt;
             s.gap = (g1c > T(0)) ? s.gapp(cur) : nullptr;
@@ -3677,7 +3601,7 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
     }
     // all step lengths at once; the largest one that passes the Armijo test is taken
     T Ja;
-    LFSD_WCK(0, Ja = s.rollout_alphas(cur, true, alpha_l));
+    Ja = s.rollout_alphas(cur, true, alpha_l);
     ldsRed[s.lane] = Ja;
     __syncthreads();
     int ia = -1, ib = -1;
@@ -3726,16 +3650,13 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
         else status = ST_FAILED;
       } else {
         mu_bad = mu; mu_hold = 0;
-        mu = t_max(mu * T(LFSD_MU_UP), mode == 2 ? T(1e-4) : T(1e-6));
+        mu = t_max(mu * T(kMuUp), mode == 2 ? T(1e-4) : T(1e-6));
       }
     }
-#if defined(LFSD_TRACE)
-    if (s.lane == 0 && traj == 0) printf("wide it %d st %d mode %d g %.6e J %.12e (ref %.10e gaps %d close %d) ia %d accept %d mu %g dV1 %.4e dV2 %.4e Jmin %.12e\n", it, status, mode, (double)gnorm, (double)J, (double)Jr, (int)have_gaps, (int)close_now, ia, (int)accept, (double)mu, (double)dV1, (double)dV2, (double)Jmin);
-#endif
     if (accept) {
       const T mu_taken = mu;
       s.adopt_alpha(ia, cur ^ 1);
-      LFSD_WCK(1, s.linearise_parallel(cur ^ 1));
+      s.linearise_parallel(cur ^ 1);
       cur ^= 1;
       // (the roll-out that CLOSES an iterate with gaps is no Newton step: that the gradient did not contract over it says nothing
       //  about convergence -- round 5 let the "gradient stopped contracting" test end such solves one sweep later, 32x above the
@@ -3747,18 +3668,16 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
       if (ia == 0) {
         // (a ratio-tested faster descent of the shift was measured on the rocket and needs MORE iterations in every variant --
         //  a shift that falls faster fails the next factorisation more often: profiles/HISTORY.md, r04_e_rocket_gain_ratio_ab.txt)
-        const T mu_next = (mu > T(1e-8)) ? mu * T(LFSD_MU_DOWN) : T(0);
+        const T mu_next = (mu > T(1e-8)) ? mu * T(kMuDown) : T(0);
         if (mu > T(0) && mu_bad >= T(0) && mu_next <= mu_bad && mu_hold < mu_hold_need) ++mu_hold;
         else { mu = mu_next; mu_hold = 0; }
-        if (mode == 0 && ham_ok && (Jr - Jn) < T(LFSD_HAM_SWITCH) * t_abs(Jn)) mode = 1;
+        if (mode == 0 && ham_ok && (Jr - Jn) < T(kHamSwitch) * t_abs(Jn)) mode = 1;
         else if (mode == 0 && !ham_ok && (Jr - Jn) < T(1e-2) * t_abs(Jn)) gn_crawl = true;
       }
-      // past the big drops: the reference's grid.  LFSD_COARSE_EXIT_RULE 0: any accepted step that gains less than the switch;
-      // 1: full steps only (a short step through a badly modelled patch gains little too, and is no sign of convergence);
-      // 2: full steps at a shift below LFSD_COARSE_EXIT_MU; 3: never by the gain (only the convergence tests above)
-      if (coarse && (Jr - Jn) < T(LFSD_COARSE_SWITCH) * t_abs(Jn)) {
-        if ((LFSD_COARSE_EXIT_RULE) == 0 || ((LFSD_COARSE_EXIT_RULE) == 1 && ia == 0) ||
-            ((LFSD_COARSE_EXIT_RULE) == 2 && ia == 0 && mu_taken <= T(LFSD_COARSE_EXIT_MU))) relin = true;
+      // past the big drops: the reference's grid, after a full step (a short step through a badly modelled patch gains little too,
+      // and is no sign of convergence) at a shift below kCoarseExitMu
+      if (coarse && (Jr - Jn) < T(kCoarseSwitch) * t_abs(Jn)) {
+        if (ia == 0 && mu_taken <= T(kCoarseExitMu)) relin = true;
       }
       J = Jn;
       J_feas = J;
@@ -3791,18 +3710,6 @@ __global__ void __launch_bounds__(64 * W, 1) oc_solve_wide_kernel(OcArgs<T> a) {
     return;
   }
   if (status == ST_RUNNING) status = ST_MAXITER;
-#if defined(LFSD_MS_STATS)      // development aid (tools/ms_dev.py): iterations and multiple-shooting steps per trajectory
-  if (threadIdx.x == 0) printf("msstat %d %d %d\n", (int)blockIdx.x, it, n_ms);
-#endif
-#if defined(LFSD_OC_CLOCK)
-#ifndef LFSD_OC_CLOCK_TOTAL
-#define LFSD_OC_CLOCK_TOTAL (1LL << 62)
-#endif
-  if (threadIdx.x == 0 && (it >= LFSD_OC_CLOCK || blockIdx.x == 0 || clock64() - wck_t0 >= (long long)(LFSD_OC_CLOCK_TOTAL)))
-    printf("wide clock traj %d: iterations %d (%d multiple-shooting steps) total %lld rollout_alphas %lld linearise %lld costates %lld hessians %lld backward %lld ms_forward %lld ms_trial %lld | left the coarse grid at iteration %d, clock %lld\n",
-           (int)blockIdx.x, it, n_ms, clock64() - wck_t0, wck[0], wck[1], wck[2], wck[3], wck[4], wck[5], wck[6], wck_it_exit, wck_exit);
-#endif
-#undef LFSD_WCK
   if (!costates_ok) s.costate_sweep(cur);                 // costates of the final nominal
   __syncthreads();
   {

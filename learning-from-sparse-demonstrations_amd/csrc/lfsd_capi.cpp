@@ -6,9 +6,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
-#ifndef LFSD_WIDE_MAX_BATCH
-#define LFSD_WIDE_MAX_BATCH 1536
-#endif
 #if !defined(LFSD_SPLIT_RICCATI)
 #include "lfsd_riccati.inc"
 #endif
@@ -57,7 +54,7 @@ static bool use_wide(int dtype, int batch, int exact_after, int mapping, bool bo
   if (mapping == LFSD_MAP_WIDE) return true;
   if (exact_after == 0) return true;      // Newton from the first iteration (rocket): wide wins at every batch size measured
   const bool lean_mfma = OC_PK && dtype == LFSD_F32;
-  return batch <= LFSD_WIDE_MAX_BATCH && !lean_mfma;
+  return batch <= lfsd::kWideMaxBatch && !lean_mfma;
 }
 
 // fp64 on the lock-step mapping, 32-lane models (the class with a mesh continuation), no bounds, not Newton-from-start: a cold
@@ -70,7 +67,7 @@ static bool use_wide(int dtype, int batch, int exact_after, int mapping, bool bo
 static bool seeded_f64(int dtype, int batch, int exact_after, int mapping, bool bounded) {
   const char* e = getenv("LFSD_F64_SEED");
   if (e && atoi(e) == 0) return false;
-  return (LFSD_F64_SEED != 0) && OC_PK && dtype == LFSD_F64 && !bounded && exact_after != 0 &&
+  return OC_PK && dtype == LFSD_F64 && !bounded && exact_after != 0 &&
          !use_wide(dtype, batch, exact_after, mapping, bounded);
 }
 // staging area behind the fp64 scratch (byte offsets from its end, 256-byte aligned)
@@ -160,7 +157,7 @@ static int coc_solve_t(int batch, int n_grid, int steps_per_grid, const void* in
   a.ws = (T*)workspace; a.ws_stride = lfsd::OcLayout<Model>::template ws_elems<G>(n_grid);
   a.tol = (T)tol;
   a.exact_after = exact_after;
-  a.mu_stage_frac = (exact_after == 0) ? (T)(LFSD_MU_STAGE_FRAC_NEWTON) : T(0);
+  a.mu_stage_frac = (exact_after == 0) ? (T)(lfsd::kMuStageFracNewton) : T(0);
   a.start_mode = start_mode;
   if (use_wide(sizeof(T) == 4 ? LFSD_F32 : LFSD_F64, batch, exact_after, mapping, control_lb != nullptr)) {       // bounded problems: the wide kernel at every batch size
     a.ws_stride = lfsd::OcLayout<Model>::ws_elems_wide(n_grid);

@@ -76,13 +76,7 @@ def _hipcc_flags(spec, extra=()):
     g = lanes_for(spec.n, spec.m, spec.p)
     return [find_hipcc(), "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC",
             "-fno-signed-zeros", "-fvisibility=hidden",
-            "-DLFSD_G=%d" % g, '-DLFSD_MODEL_HEADER="gen/%s.h"' % spec.hash(), "-I" + CSRC_DIR] + list(extra) + \
-        os.environ.get("LFSD_EXTRA_HIPCC_FLAGS", "").split()       # tuning experiments (tools/tune.py)
-
-
-def hipcc_command(spec, out, extra=()):
-    """The library as ONE translation unit (tuning tools; the product build is hipcc_commands)."""
-    return _hipcc_flags(spec, extra) + ["-shared", os.path.join(CSRC_DIR, "lfsd_capi.cpp"), "-o", out]
+            "-DLFSD_G=%d" % g, '-DLFSD_MODEL_HEADER="gen/%s.h"' % spec.hash(), "-I" + CSRC_DIR] + list(extra)
 
 
 # Per translation unit.  Rounds 1-5 compiled the first unit with `-mllvm -amdgpu-sched-strategy=max-ilp` (round 1: 5 % off oc_solve;
@@ -207,13 +201,6 @@ def _checked_build(spec, out, extra=(), verbose=False, what="model"):
         shutil.rmtree(work, ignore_errors=True)
 
 
-def build_checked(spec, out, flags=(), verbose=False):
-    """A diagnostic / experiment build (tools/): the product's two-unit build with extra flags into `out`, assembly-checked the same way
-    -- an instrumented build that is silently wrong misleads (round 6: a clock-reading build of the wide kernel was)."""
-    write_header(spec)
-    return _checked_build(spec, out, extra=list(flags), verbose=verbose, what="diagnostic build of model")
-
-
 def build_library(spec, force=False, verbose=False):
     """Generate the model header and compile the gfx950 shared library in-tree (csrc/build/), assembly checked (above)."""
     os.makedirs(BUILD_DIR, exist_ok=True)
@@ -232,7 +219,7 @@ def variant_library_path(spec, tag):
 
 
 def build_variant_library(spec, tag, flags):
-    """hipcc build of a VARIANT of a model library (experiment switches of csrc/cpdp_common.h set on the command line) into
+    """hipcc build of a VARIANT of a model library (build switches of csrc/cpdp_common.h set on the command line) into
     csrc/build/ab_<hash>_<tag>.so, rebuilt when a kernel source is newer.  The A/B tests of the GPU tier compare the product
     build with such variants; never loaded by the product path.  Same assembly check as the product build."""
     write_header(spec)

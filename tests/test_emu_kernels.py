@@ -65,7 +65,7 @@ def test_pendulum_full_pipeline_vs_oracle(emu, dtype, oc_mapping):
 
 def test_aux_sweeps_converge_at_fourth_order(emu):
     """fp64 (classical RK4 inside the Strang split): halving the split-step size must cut the gradient error ~16x (Strang +
-    Richardson) until round-off.  (The fp32 kernels use the explicit midpoint rule, LFSD_AUX_RK32: third order, below
+    Richardson) until round-off.  (The fp32 kernels use the explicit midpoint rule, kAuxRk32: third order, below
     their rounding floor either way.)"""
     thetas, taus, wps = [[2.0, 1.0, 1.0]], [0.1, 0.3, 0.6, 0.7, 0.9], [[0.4], [1.2], [2.1], [2.4], [2.9]]
     o = make_oracle("pendulum", 10)
@@ -94,7 +94,7 @@ def test_error_controlled_substepping_beats_fixed_units(emu):
         err[key] = (rel(aux["grad"][0], r["grad"]), rel(aux["auxX_grid"][0].numpy().transpose(0, 2, 1).reshape(-1, n * p), r["vX"]))
     assert err["fixed4"][0] > 5e-4                                    # what the fixed default leaves on this grid
     # library default, rtol 1e-3: both errors inside the requested tolerance, the gradient well inside (the controller does
-    # not integrate finer than the tolerance asks for -- LFSD_AUX_DOWN -- so dx/dtheta sits at 6e-4 here, not far below)
+    # not integrate finer than the tolerance asks for -- kAuxDown -- so dx/dtheta sits at 6e-4 here, not far below)
     assert err["default"][0] < 2e-4 and err["default"][1] < 1e-3, err
     assert err["rtol1e-4"][0] < 1e-5 and err["rtol1e-4"][1] < 5e-5, err
     assert err["rtol1e-6"][0] <= err["rtol1e-4"][0] * 1.5 and err["rtol1e-6"][1] < 1e-5, err
