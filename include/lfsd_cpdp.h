@@ -17,6 +17,8 @@
  *                           (Examples/*.py getloss_corrections)
  *   lfsd_optimizer_step   lib/QuadAlgorithm.py:454-578 Vanilla/Nesterov/Adam/Nadam/AMSGrad
  *   lfsd_lookahead        lib/QuadAlgorithm.py:478 (Nesterov look-ahead point)
+ *   lfsd_stop_compact     lib/QuadAlgorithm.py:239-257 (the learning loop's stop test, per seed; ABI 10)
+ *   lfsd_gather_rows / lfsd_scatter_rows   the dense batch of the seeds still learning (ABI 10)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -25,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 9
+#define LFSD_ABI_VERSION 10
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -196,6 +198,31 @@ int lfsd_optimizer_step(int dtype, int method, int batch, int n_param, int iter_
 
 /* out = theta + mu * v   (Nesterov look-ahead, [B][n_param]) */
 int lfsd_lookahead(int dtype, long long n, double mu, const void* theta, const void* v, void* out, void* stream);
+
+/* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
+ * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds
+ * one after the other).  One launch (one workgroup) applies that test to the `n_rows` rows of a batch of seeds still learning and
+ * compacts the survivors, stably and deterministically (no atomics):
+ *   loss [n_rows], grad [n_rows][n_param] of arithmetic type `dtype`; the norm is formed in that type
+ *   keep(i) = loss[i] > loss_tol && ||grad[i]||_2 > grad_tol       (a NaN loss or gradient stops the seed, as the reference's test)
+ *   rows_in  [n_rows] original row ids in ascending order, NULL = identity
+ *   eligible [n_rows] or NULL: rows with 0 are kept whatever their loss / gradient (frozen this step, gradient zeroed)
+ *   rows_out [n_rows] original id of the k-th survivor, pos_out [n_rows] its position in the input list (entries from *n_out on
+ *            are left alone), n_out [1] their number; rows_out must not be rows_in
+ *   active, stop_iter: FULL-batch arrays indexed by original id; a row that stops now gets active = 0, stop_iter = iter_idx + 1
+ * n_rows > 0, n_param > 0, iter_idx >= 0, thresholds not NaN. */
+int lfsd_stop_compact(int dtype, int n_rows, int n_param, const void* loss, const void* grad,
+                      const int* rows_in, const int* eligible,
+                      double loss_tol, double grad_tol, int iter_idx,
+                      int* rows_out, int* pos_out, int* n_out, int* active, int* stop_iter, void* stream);
+
+/* ABI 10 -- rows of `row_bytes` bytes between a full batch and the dense batch of the seeds still learning (what the solver
+ * entry points above are then called with: lib/QuadAlgorithm.py:239-257 per seed):
+ *   lfsd_gather_rows   dst[i][:] = src[index[i]][:]      lfsd_scatter_rows   dst[index[i]][:] = src[i][:]      i < n_rows
+ * Type-blind bit copies.  row_bytes and both base addresses must be multiples of 4; 16-byte accesses are used when all three
+ * are multiples of 16.  index [n_rows] int32, entries distinct for a scatter; src and dst must not overlap. */
+int lfsd_gather_rows(int n_rows, long long row_bytes, const int* index, const void* src, void* dst, void* stream);
+int lfsd_scatter_rows(int n_rows, long long row_bytes, const int* index, const void* src, void* dst, void* stream);
 
 #ifdef __cplusplus
 }

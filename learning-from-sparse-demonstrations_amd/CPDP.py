@@ -499,12 +499,26 @@ class SparseDemoLearner:
     ``event_hook(name)``, if set, is called right before each device phase of ``step`` ("oc_solve", "aux_riccati",
     "aux_forward", "update") and once after the last one ("end"), so a caller can bracket the kernels with HIP events
     (bench.py) without re-implementing the iteration.
+
+    ``stop_rule`` (``independent`` mode only; default ``None`` = no rule, the iteration above and nothing else):
+    ``dict(loss=0.9, grad_norm=0.05)`` gives every seed the reference loop's own stop test (lib/QuadAlgorithm.py:239-257: go on
+    while ``loss > 0.9 and norm(diff_loss) > 0.05``; the reference learns its seeds one at a time, Examples/robotarm_random.py:
+    60-73).  The test runs on the device after each update (``lfsd_stop_compact``: test + stable compaction of the seeds still
+    learning, one launch; the host reads one int, their number).  A seed that fails it has had its last update -- the reference
+    updates, then tests at the top of the next iteration -- and is frozen from then on: ``theta`` / ``m`` / ``v`` / ``vhat`` stay
+    [B, p] and its row is masked out of ``lfsd_optimizer_step``.  Once seeds have stopped, the solve and both sweeps run on a DENSE
+    batch of the others (``lfsd_gather_rows`` in, ``lfsd_scatter_rows`` out; inputs that do not change are gathered again only
+    when the set shrank; with ``warm_start`` / ``skip_unconverged`` a seed's previous controls move with it), mapped onto the
+    machine as ``lfsd_coc_solve`` maps a batch of that size.  ``active`` [B] bool, ``stop_iter`` [B] (iterations a stopped seed
+    took; 0 = still learning) and ``n_active`` report the state; ``step`` returns full-size (loss, grad) in which a stopped seed
+    keeps its last values, and launches nothing once ``n_active == 0``.  A loop timed with the rule on pays that one host read per
+    step.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
-                 skip_unconverged=None):
+                 skip_unconverged=None, stop_rule=None):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
         self.b1, self.b2, self.eps = beta_1, beta_2, epsilon
         if method not in runtime.OPT_METHODS:
@@ -552,6 +566,41 @@ class SparseDemoLearner:
         self._sol = None
         self._aux = None
         self._Z = None
+        self._stop = None
+        if stop_rule is not None:
+            if mode != "independent":
+                raise LfsdError("stop_rule is a per-seed rule: mode='independent' only (shared mode keeps one theta for all)")
+            unknown = set(stop_rule) - {"loss", "grad_norm"}
+            if unknown or not {"loss", "grad_norm"} <= set(stop_rule):
+                raise LfsdError("stop_rule takes exactly the keys 'loss' and 'grad_norm' (got %s)" % sorted(stop_rule))
+            dev, i32 = self.x0.device, torch.int32
+            self._stop = dict(loss=float(stop_rule["loss"]), grad_norm=float(stop_rule["grad_norm"]))
+            self._active = torch.ones(B, dtype=i32, device=dev)
+            self._stop_iter = torch.zeros(B, dtype=i32, device=dev)
+            self._rows = [torch.arange(B, dtype=i32, device=dev), torch.empty(B, dtype=i32, device=dev)]      # ping-pong
+            self._cur = 0
+            self._pos = torch.empty(B, dtype=i32, device=dev)
+            self._n_out = torch.zeros(1, dtype=i32, device=dev)
+            self._dense = None           # dense copies of the per-row inputs, allocated when the first seed stops
+            self._regather = False
+            self._full = None            # the full-size solver buffers (leading slices of them hold the dense batch)
+            self._prev = None            # (controls, status) of the previous solve of the rows now active, dense
+            self._loss_full = self._grad_full = None
+        self.n_active = B
+
+    @property
+    def active(self):
+        """[B] bool: seeds still learning (all of them without a stop rule)."""
+        if self._stop is None:
+            return torch.ones(self.B, dtype=torch.bool, device=self.x0.device)
+        return self._active != 0
+
+    @property
+    def stop_iter(self):
+        """[B] int32: outer iterations a stopped seed took (the reference loop's count), 0 while it is still learning."""
+        if self._stop is None:
+            return torch.zeros(self.B, dtype=torch.int32, device=self.x0.device)
+        return self._stop_iter
 
     def evaluate(self, theta):
         """(loss [B], grad [B,p]) of every trajectory at parameters theta ([B,p] or [1,p])."""
@@ -583,14 +632,14 @@ class SparseDemoLearner:
             loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
         return loss, grad
 
-    def mask_unconverged(self, status, loss, grad):
+    def mask_unconverged(self, status, loss, grad, stats=None):
         """Rows whose OC solve neither converged (1) nor stalled at working precision (2), whose loss / gradient is
         not finite (parameters that have left the region where the problem is well posed, e.g. a cost weight driven
         negative), or whose sensitivity sweeps report an interval accepted above `aux_rtol` (the `stats` output of
         lfsd_aux_solve: refinement stopped gaining next to a conjugate point) are frozen for this step: ``self._ok`` masks them out of the update kernel; their gradient (and, in
         shared mode, their loss, which enters a sum) is zeroed."""
         ok = ((status == 1) | (status == 2)) & torch.isfinite(loss) & torch.isfinite(grad).all(dim=1)
-        st = self._aux.get("stats") if self._aux is not None else None
+        st = stats if stats is not None else (self._aux.get("stats") if self._aux is not None else None)
         if st is not None:      # ... or whose auxiliary sweeps accepted an interval above their tolerance (next to a conjugate point)
             ok = ok & ((st[:, 1] + st[:, 3]) == 0)
         self._ok = ok
@@ -609,8 +658,126 @@ class SparseDemoLearner:
             return None
         return {k: self._aux[k] for k in ("loss", "grad", "stats")}
 
+    # ---- per-seed stop rule: the dense batch of the seeds still learning ------------------------------------------
+    def _evaluate_active(self, theta_eval):
+        """(loss [n], grad [n,p]) of the n_active < B seeds still learning, solved as a dense batch in the leading slices of the
+        buffers the full batch used.  theta_eval [B,p]."""
+        lib, n = self.lib, self.n_active
+        rows, d = self._rows[self._cur], self._dense
+        lib.gather_rows(rows, theta_eval, d["theta"], n)
+        if self._regather:               # x0 / horizon / waypoints / per-trajectory constants: only when the set shrank
+            for k, src in d["sources"].items():
+                lib.gather_rows(rows, src, d[k], n)
+            self._regather = False
+        consts = d["consts"][:n] if "consts" in d else self.consts
+        u_init = None
+        if self._prev is not None:
+            prev, status = self._prev[0][:n, :-1], self._prev[1][:n]
+            if self.warm_start:
+                u_init = prev.contiguous()
+            elif self.skip_unconverged:      # (as evaluate(): a solve at the iteration limit is continued, every other one cold-starts)
+                cont = (status == 3).reshape(-1, 1, 1)
+                u_init = torch.where(cont & torch.isfinite(prev), prev, torch.zeros_like(prev)).contiguous()
+        hook = self.event_hook
+        if hook is not None:
+            hook("oc_solve")
+        full = self._full
+        sol = self.oc.cocSolverBatch(d["x0"][:n], d["hz"][:n], d["theta"][:n], consts=consts, u_init=u_init, workspace=self._ws,
+                                     out={k: full["sol"][k][:n] for k in ("state_grid", "control_grid", "costate_grid", "cost",
+                                                                          "iters", "status")})
+        self._ws = sol["workspace"]
+        phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
+        aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, Z_grid=full["Z"][:n],
+                                        out={k: full["aux"][k][:n] for k in ("loss", "grad", "stats")}, phase_hook=phase,
+                                        validate=False, skip_status=(3, 4) if self.skip_unconverged else None)
+        self._sol_active, self._aux_active = sol, aux
+        self._prev = (sol["control_grid"], sol["status"])
+        loss, grad = aux["loss"].to(self.theta.dtype), aux["grad"].to(self.theta.dtype)
+        if self.skip_unconverged:
+            loss, grad = self.mask_unconverged(sol["status"], loss, grad, stats=aux.get("stats"))
+        return loss, grad
+
+    def _apply_stop_rule(self, loss, grad):
+        """Stop test + compaction of the rows just evaluated (loss [n], grad [n,p], n = n_active), then the bookkeeping of a
+        set that shrank.  The one host read of the rule is here."""
+        lib, n, B = self.lib, self.n_active, self.B
+        rows = self._rows[self._cur]
+        elig = None if self._ok is None else self._ok.to(torch.int32)      # frozen this step: its gradient was zeroed, not small
+        lib.stop_compact(loss, grad, self._stop["loss"], self._stop["grad_norm"], self.iter_idx - 1, self._rows[1 - self._cur],
+                         self._pos, self._n_out, self._active, self._stop_iter, rows_in=None if n == B else rows[:n],
+                         eligible=elig)
+        n_new = int(self._n_out.item())
+        if n_new == n:
+            return
+        if self._dense is None:          # the first seeds stop: from here on the solver buffers hold a dense batch
+            self._loss_full, self._grad_full = loss.clone(), grad.clone()
+            self._full = dict(sol=self._sol_out(), aux=self._aux_out(), Z=self._Z)
+            src = dict(x0=self.x0, hz=self.hz, taus=self.taus, wps=self.wps)
+            if self.consts is not None and self.consts.dim() == 2:
+                src["consts"] = self.consts
+            self._dense = {k: torch.empty_like(t) for k, t in src.items()}
+            self._dense.update(theta=torch.empty_like(self.theta), sources=src)
+            self._prev = (self._sol["control_grid"], self._sol["status"])
+        if n_new > 0 and (self.warm_start or self.skip_unconverged):
+            # a continued solve continues ITS OWN row: the survivors' controls / status move to their new positions
+            u, st = self._prev
+            carry = (torch.empty((n_new,) + tuple(u.shape[1:]), dtype=u.dtype, device=u.device),
+                     torch.empty((n_new,), dtype=st.dtype, device=st.device))
+            lib.gather_rows(self._pos, u[:n], carry[0], n_new)
+            lib.gather_rows(self._pos, st[:n], carry[1], n_new)
+            self._prev = carry
+        else:
+            self._prev = None
+        self._cur, self.n_active, self._regather = 1 - self._cur, n_new, True
+
+    def _evaluate_stop_rule(self, theta_eval):
+        """(loss, grad) of the rows still learning -- [n_active] rows, what the stop test reads -- and full-size [B]."""
+        self._ok = None
+        n = self.n_active
+        if n == self.B:
+            loss, grad = self.evaluate(theta_eval)
+            return loss, grad, loss, grad
+        loss, grad = self._evaluate_active(theta_eval)
+        rows = self._rows[self._cur]
+        self.lib.scatter_rows(rows, loss.contiguous(), self._loss_full, n)
+        self.lib.scatter_rows(rows, grad.contiguous(), self._grad_full, n)
+        return loss, grad, self._loss_full, self._grad_full
+
+    def _step_stop_rule(self):
+        """step() with a stop rule.  While no seed has stopped: evaluate() + update as ever, plus the test.  After: gather the
+        evaluation point, solve / differentiate n_active rows, scatter loss / gradient, masked update, test."""
+        if self.n_active == 0:
+            return self._loss_full, self._grad_full
+        lib, B, n = self.lib, self.B, self.n_active
+        theta_eval = self.theta
+        if self.method == "Nesterov":
+            theta_eval = lib.lookahead(self.theta, self.m, self.mu)      # QuadAlgorithm.py:478
+        loss, grad, loss_full, grad_full = self._evaluate_stop_rule(theta_eval)
+        hook = self.event_hook
+        if hook is not None:
+            hook("update")
+        row_active = None if n == B else self._active      # (as of the last test: a seed that stops in this step is updated)
+        if self._ok is not None:                           # skip_unconverged: rows frozen for this step only
+            ok = self._ok.to(torch.int32)
+            row_active = ok if n == B else lib.scatter_rows(self._rows[self._cur], ok, self._active.clone(), n)
+            if self.count_unconverged:
+                self.n_unconverged = int(n - self._ok.sum().item())
+        lib.optimizer_step(self.method, self.theta, grad_full, self.iter_idx, self.lr, self.mu, self.b1, self.b2, self.eps,
+                           m=self.m, v=self.v, vhat=self.vhat, proj_lo=self.proj_lo, row_active=row_active)
+        self.iter_idx += 1
+        if hook is not None:
+            hook("end")
+        if self.method == "Nesterov" and self.true_loss:      # QuadAlgorithm.py:487-492: the loss the reference's loop then tests
+            loss, grad, loss_full, grad_full = self._evaluate_stop_rule(self.theta)
+        self._apply_stop_rule(loss, grad)
+        if self._loss_full is not None:
+            return self._loss_full, self._grad_full
+        return loss_full, grad_full
+
     def step(self):
         """One outer iteration; returns (loss, grad) evaluated where the update rule needs them."""
+        if self._stop is not None:
+            return self._step_stop_rule()
         theta_eval = self.theta
         if self.method == "Nesterov":
             theta_eval = self.lib.lookahead(self.theta, self.m, self.mu)      # QuadAlgorithm.py:478

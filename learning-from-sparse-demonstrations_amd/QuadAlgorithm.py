@@ -7,7 +7,11 @@ Plotting / animation (QuadAlgorithm.py:260-281, 354-451, 581-613) is UI and is n
 dictionary the reference saves to ``data/uav_results_random_*.mat`` (QuadAlgorithm.py:324-333) and writes it only if
 ``save_flag`` is set.
 
-Extension: ``run(..., initial_parameters=[B,7])`` learns B independent seeds in lock-step.
+Extension: ``run(..., initial_parameters=[B,7])`` learns B independent seeds in lock-step.  ``stop="all"`` (default) leaves the
+loop when EVERY seed has passed the reference's stop test; ``stop="per_seed"`` gives every seed that test on its own
+(QuadAlgorithm.py:239-257 as the reference runs it, one seed per run): a seed that passes is frozen and leaves the launches, the
+loop ends when none is left; ``results['stop_iter']`` [B] is the number of iterations each seed took (0: still learning at
+``iter_num``), and the traces stay rectangular -- a stopped seed's last entry is repeated.
 """
 import os
 import time
@@ -112,7 +116,9 @@ class QuadAlgorithm(object):
             raise Exception("Wrong optimization method type!")
 
     def run(self, QuadInitialCondition, QuadDesiredStates, SparseInput, ObsList=(), print_flag=False, save_flag=False,
-            initial_parameters=None, save_dir=None):
+            initial_parameters=None, save_dir=None, stop="all"):
+        if stop not in ("all", "per_seed"):
+            raise ValueError("stop must be 'all' or 'per_seed'")
         t0 = time.time()
         self.ObsList = ObsList
         self.settings(QuadDesiredStates)
@@ -128,11 +134,12 @@ class QuadAlgorithm(object):
                                               np.tile(self.ini_state, (theta0.shape[0], 1)),
                                               self.time_horizon, self.time_list_sparse, self.waypoints,
                                               self.interface_pos_idx, theta0, method=self.optimization_method_str,
-                                              learning_rate=self.learning_rate, **self.opt_kwargs)
+                                              learning_rate=self.learning_rate, **self.opt_kwargs,
+                                              **(dict(stop_rule=dict(loss=0.9, grad_norm=0.05)) if stop == "per_seed" else {}))
         self.loss_trace, self.parameter_trace = [], [self.learner.theta.cpu().numpy().copy()]
         loss, diff_loss_norm = 100.0, 100.0
         for j in range(self.iter_num):
-            if (loss > 0.9) and (diff_loss_norm > 0.05):                    # QuadAlgorithm.py:242
+            if (self.learner.n_active > 0) if stop == "per_seed" else ((loss > 0.9) and (diff_loss_norm > 0.05)):   # QuadAlgorithm.py:242
                 l, g = self.learner.step()
                 loss = float(l.max())                                       # every seed must pass the stop test
                 diff_loss_norm = float(torch.linalg.norm(g, dim=1).max())
@@ -155,6 +162,8 @@ class QuadAlgorithm(object):
                    'time_grid': self.time_list_sparse, 'time_steps': time_steps,
                    'opt_state_traj': opt_traj[:, :n], 'opt_control_traj': opt_traj[:, n:n + m],
                    'horizon': horizon, 'T': self.time_horizon, 'seconds': time.time() - t0}
+        if stop == "per_seed":
+            results['stop_iter'] = self.learner.stop_iter.cpu().numpy().copy()
         if save_flag:
             import scipy.io as sio
             d = save_dir or os.path.join(os.getcwd(), 'data')

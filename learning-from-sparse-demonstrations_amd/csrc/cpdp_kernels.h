@@ -17,14 +17,16 @@
 //   aux_forward_kernel    COCSys.auxSysSolver part 2  CPDP.py:340-381 (dx/dtheta forward sweep)
 //                         + getloss_*corrections      lib/QuadAlgorithm.py:616-673
 //   optimizer_kernel      Vanilla/Nesterov/Adam/Nadam/AMSGrad updates  lib/QuadAlgorithm.py:454-578
+//   stop_compact_kernel   the loop's stop test, per seed                lib/QuadAlgorithm.py:239-257
 //
 // The same source builds for the GPU with hipcc and, with -DLFSD_EMU, for the CPU
 // SIMT emulator in tests/emu (test infrastructure; never used by the product path).
 //
 // Sources: cpdp_common.h (switches, primitives, dense helpers), cpdp_oc.h (OC solve), cpdp_aux.h (auxiliary
-// system sweeps + loss), cpdp_opt.h (update rules).
+// system sweeps + loss), cpdp_opt.h (update rules), cpdp_rows.h (per-seed stop rule, row compaction / gather / scatter).
 #pragma once
 #include "cpdp_common.h"
 #include "cpdp_oc.h"
 #include "cpdp_aux.h"
 #include "cpdp_opt.h"
+#include "cpdp_rows.h"

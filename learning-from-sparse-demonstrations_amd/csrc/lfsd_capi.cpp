@@ -464,3 +464,69 @@ LFSD_API int lfsd_lookahead(int dtype, long long n, double mu, const void* theta
   }
   return LFSD_EINVAL;
 }
+
+// ---- per-seed stop rule and the rows of a shrinking batch (cpdp_rows.h; lib/QuadAlgorithm.py:239-257) ----
+// The emulator runs every lane as a fiber with a stack of its own: its launches stay small (two wavefronts still cross the LDS
+// hand-over of the compaction).
+#if defined(LFSD_EMU)
+static constexpr int kStopBlock = 128, kCopyBlock = 64, kCopyMaxGrid = 4;
+#else
+static constexpr int kStopBlock = 1024, kCopyBlock = 256, kCopyMaxGrid = 2048;
+#endif
+
+template <typename T>
+static int stop_compact_t(int n_rows, int n_param, const void* loss, const void* grad, const int* rows_in, const int* eligible,
+                          double loss_tol, double grad_tol, int iter_idx, int* rows_out, int* pos_out, int* n_out, int* active,
+                          int* stop_iter, void* stream) {
+  lfsd::StopArgs<T> a;
+  a.n_rows = n_rows; a.n_param = n_param; a.iter_idx = iter_idx;
+  a.loss_tol = (T)loss_tol; a.grad_tol = (T)grad_tol;
+  a.loss = (const T*)loss; a.grad = (const T*)grad; a.rows_in = rows_in; a.eligible = eligible;
+  a.rows_out = rows_out; a.pos_out = pos_out; a.n_out = n_out; a.active = active; a.stop_iter = stop_iter;
+  const int block = std::min(kStopBlock, (n_rows + 63) / 64 * 64);      // whole wavefronts
+  LFSD_LAUNCH((lfsd::stop_compact_kernel<T>), 1u, (unsigned)block, stream, a);
+  return launch_status();
+}
+
+LFSD_API int lfsd_stop_compact(int dtype, int n_rows, int n_param, const void* loss, const void* grad, const int* rows_in,
+                               const int* eligible, double loss_tol, double grad_tol, int iter_idx, int* rows_out, int* pos_out,
+                               int* n_out, int* active, int* stop_iter, void* stream) {
+  if (n_rows <= 0 || n_param <= 0 || iter_idx < 0 || loss_tol != loss_tol || grad_tol != grad_tol) return LFSD_EINVAL;
+  if (!loss || !grad || !rows_out || !pos_out || !n_out || !active || !stop_iter) return LFSD_EINVAL;
+  if (rows_in && rows_in == rows_out) return LFSD_EINVAL;
+  if (dtype == LFSD_F32)
+    return stop_compact_t<float>(n_rows, n_param, loss, grad, rows_in, eligible, loss_tol, grad_tol, iter_idx, rows_out, pos_out,
+                                 n_out, active, stop_iter, stream);
+  if (dtype == LFSD_F64)
+    return stop_compact_t<double>(n_rows, n_param, loss, grad, rows_in, eligible, loss_tol, grad_tol, iter_idx, rows_out, pos_out,
+                                  n_out, active, stop_iter, stream);
+  return LFSD_EINVAL;
+}
+
+static int copy_rows_launch(bool scatter, int n_rows, long long row_bytes, const int* index, const void* src, void* dst,
+                            void* stream) {
+  if (n_rows <= 0 || row_bytes <= 0 || !index || !src || !dst) return LFSD_EINVAL;
+  const unsigned long long bits = (unsigned long long)row_bytes | (unsigned long long)(size_t)src | (unsigned long long)(size_t)dst;
+  if (bits & 3ull) return LFSD_EINVAL;
+  const bool wide = (bits & 15ull) == 0;
+  lfsd::RowCopyArgs a;
+  a.n_rows = n_rows; a.row_words = row_bytes / (wide ? 16 : 4); a.index = index; a.src = src; a.dst = dst;
+  const long long total = (long long)n_rows * a.row_words;
+  const unsigned grid = (unsigned)std::min<long long>((total + kCopyBlock - 1) / kCopyBlock, kCopyMaxGrid);
+  if (scatter) {
+    if (wide) { LFSD_LAUNCH((lfsd::scatter_rows_kernel<lfsd::RowWord16>), grid, kCopyBlock, stream, a); }
+    else { LFSD_LAUNCH((lfsd::scatter_rows_kernel<unsigned>), grid, kCopyBlock, stream, a); }
+  } else {
+    if (wide) { LFSD_LAUNCH((lfsd::gather_rows_kernel<lfsd::RowWord16>), grid, kCopyBlock, stream, a); }
+    else { LFSD_LAUNCH((lfsd::gather_rows_kernel<unsigned>), grid, kCopyBlock, stream, a); }
+  }
+  return launch_status();
+}
+
+LFSD_API int lfsd_gather_rows(int n_rows, long long row_bytes, const int* index, const void* src, void* dst, void* stream) {
+  return copy_rows_launch(false, n_rows, row_bytes, index, src, dst, stream);
+}
+
+LFSD_API int lfsd_scatter_rows(int n_rows, long long row_bytes, const int* index, const void* src, void* dst, void* stream) {
+  return copy_rows_launch(true, n_rows, row_bytes, index, src, dst, stream);
+}

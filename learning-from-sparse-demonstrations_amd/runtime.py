@@ -101,7 +101,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "lfsd_capi.cpp", "lfsd_internal.h",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "lfsd_capi.cpp", "lfsd_internal.h",
                   "lfsd_riccati.inc", "lfsd_riccati.cpp")
 
 
@@ -266,7 +266,8 @@ class ModelLibrary:
     """One loaded model library (all entry points of include/lfsd_cpdp.h)."""
 
     EXPORTS = ("lfsd_get_model_info", "lfsd_interface_dim", "lfsd_const_default", "lfsd_coc_workspace_bytes", "lfsd_coc_solve",
-               "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead")
+               "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
+               "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -293,9 +294,12 @@ class ModelLibrary:
                                        ci, cd, vp, vp, ci, vp]
         L.lfsd_optimizer_step.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_lookahead.argtypes = [ci, ctypes.c_longlong, cd, vp, vp, vp, vp]
+        L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
+        L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
+        L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 9:
+        if rc != 0 or info.abi_version != 10:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -512,3 +516,58 @@ class ModelLibrary:
                                          self._p(out), self._stream(theta))
         self._rc(rc, "lfsd_lookahead")
         return out
+
+    def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
+                     eligible=None):
+        """The reference loop's stop test per row (lib/QuadAlgorithm.py:242) + stable compaction of the survivors, one launch
+        (include/lfsd_cpdp.h, ABI 10).  loss [R], grad [R, p]; rows_in / eligible [R] int32 or None; rows_out / pos_out [>= R],
+        n_out [1], active / stop_iter [full batch] int32.  Nothing is read back here."""
+        dt = loss.dtype
+        R, p = grad.shape
+        self._check(loss, (R,), dt, "loss")
+        self._check(grad, (R, p), dt, "grad")
+        self._check(rows_in, (R,), torch.int32, "rows_in", optional=True)
+        self._check(eligible, (R,), torch.int32, "eligible", optional=True)
+        for nm, t in (("rows_out", rows_out), ("pos_out", pos_out)):
+            self._check(t, t.shape if isinstance(t, torch.Tensor) else None, torch.int32, nm)
+            if t.dim() != 1 or t.shape[0] < R:
+                raise LfsdError("%s needs room for %d rows" % (nm, R))
+        self._check(n_out, (1,), torch.int32, "n_out")
+        if not isinstance(active, torch.Tensor) or not isinstance(stop_iter, torch.Tensor) or active.shape != stop_iter.shape:
+            raise LfsdError("active and stop_iter are full-batch int32 tensors of one shape")
+        self._check(active, active.shape, torch.int32, "active")
+        self._check(stop_iter, active.shape, torch.int32, "stop_iter")
+        if active.dim() != 1 or (rows_in is None and active.shape[0] < R):
+            raise LfsdError("active / stop_iter are indexed by original row id: [B] with B >= the number of rows")
+        with self._on(loss):
+            rc = self.lib.lfsd_stop_compact(_DT[dt], R, p, self._p(loss), self._p(grad), self._p(rows_in), self._p(eligible),
+                                            float(loss_tol), float(grad_tol), int(iter_idx), self._p(rows_out), self._p(pos_out),
+                                            self._p(n_out), self._p(active), self._p(stop_iter), self._stream(loss))
+        self._rc(rc, "lfsd_stop_compact")
+
+    def _copy_rows(self, scatter, index, src, dst, n_rows):
+        name = "lfsd_scatter_rows" if scatter else "lfsd_gather_rows"
+        fn = getattr(self.lib, name)
+        for nm, t in (("src", src), ("dst", dst)):
+            self._check(t, t.shape if isinstance(t, torch.Tensor) else None, src.dtype if isinstance(src, torch.Tensor) else None, nm)
+        self._check(index, index.shape if isinstance(index, torch.Tensor) else None, torch.int32, "index")
+        if src.dim() < 1 or dst.dim() != src.dim() or tuple(src.shape[1:]) != tuple(dst.shape[1:]):
+            raise LfsdError("%s: src %s and dst %s are rows of different shapes" % (name, tuple(src.shape), tuple(dst.shape)))
+        n_rows = int(n_rows)
+        dense, sparse = (src, dst) if scatter else (dst, src)
+        if index.dim() != 1 or not 0 < n_rows <= min(index.shape[0], dense.shape[0]) or sparse.shape[0] < 1:
+            raise LfsdError("%s: %d rows do not fit index %s / the dense side %s" % (name, n_rows, tuple(index.shape), tuple(dense.shape)))
+        row_bytes = src.element_size() * (src[0].numel() if src.dim() > 1 else 1)
+        with self._on(src):
+            rc = fn(n_rows, row_bytes, self._p(index), self._p(src), self._p(dst), self._stream(src))
+        self._rc(rc, name)
+        return dst
+
+    def gather_rows(self, index, src, dst, n_rows):
+        """dst[i] = src[index[i]] for i < n_rows (bit copy of whole rows, any dtype; include/lfsd_cpdp.h, ABI 10).  The caller
+        vouches for the entries of `index` (a device array: they are not read back) lying inside src."""
+        return self._copy_rows(False, index, src, dst, n_rows)
+
+    def scatter_rows(self, index, src, dst, n_rows):
+        """dst[index[i]] = src[i] for i < n_rows (distinct entries of `index`, inside dst)."""
+        return self._copy_rows(True, index, src, dst, n_rows)
