@@ -19,6 +19,8 @@
  *   lfsd_lookahead        lib/QuadAlgorithm.py:478 (Nesterov look-ahead point)
  *   lfsd_stop_compact     lib/QuadAlgorithm.py:239-257 (the learning loop's stop test, per seed; ABI 10)
  *   lfsd_gather_rows / lfsd_scatter_rows   the dense batch of the seeds still learning (ABI 10)
+ *   lfsd_grid_curvature   CPDP/CPDP.py:388-390  COCSys.interpolation(x, y, 2): the cubic interpolant of a grid (ABI 11)
+ *   lfsd_aux_*_cubic      CPDP/CPDP.py:301-381  auxSysSolver handed that interpolant (interplation_level=2; ABI 11)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -27,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 10
+#define LFSD_ABI_VERSION 11
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -184,6 +186,49 @@ int lfsd_aux_forward(int dtype, int batch, int n_grid,
                      void* loss, void* grad, void* auxX_grid, void* auxU_grid,
                      int substeps, double rtol, int* stats,
                      const int* oc_status, int skip_status_mask, void* stream);
+
+/* ABI 11 -- interpolation level 2.  The reference's cocSolver(..., interplation_level=2) returns scipy's interp1d(kind='cubic') of
+ * the solved grids -- the not-a-knot cubic spline -- and its auxSysSolver integrates the Riccati and sensitivity ODEs along whatever
+ * interpolant it is handed (CPDP.py:320-323, 347, 388-390).  On the uniform time grid the spline is carried as one CURVATURE grid per
+ * solution grid, c_k = h^2 y''(t_k) / 6: on interval k at fraction s
+ *     y(s) = y_k + s (y_k+1 - y_k) + ((1-s)^3 - (1-s)) c_k + (s^3 - s) c_k+1 .
+ * lfsd_grid_curvature fits it for every component of a grid:
+ *   grid, curv [B][n_grid+1][n_comp] of arithmetic type `dtype` (distinct arrays); n_grid >= 3 (four nodes, as scipy asks),
+ *   batch > 0, n_comp > 0, else LFSD_EINVAL.  Any model library serves any grid (nothing of the model enters). */
+int lfsd_grid_curvature(int dtype, int batch, int n_grid, int n_comp, const void* grid, void* curv, void* stream);
+
+/* lfsd_aux_solve / lfsd_aux_riccati / lfsd_aux_forward along that cubic interpolant: the arguments of their namesakes plus
+ *   state_curv [B][n_grid+1][n_state], control_curv [B][n_grid+1][n_control], costate_curv [B][n_grid+1][n_state]
+ * (lfsd_grid_curvature of the three grids; all three required, n_grid >= 3).  The nominal (x, u, lambda)(t) inside the sweeps and
+ * x(tau) of the loss follow the spline.  What the reference keeps linear stays linear: [P W] between its grid values inside the
+ * forward sweep, dx/dtheta(tau) in the gradient, and the returned auxX_grid / auxU_grid are grid values as before
+ * (CPDP.py:338, 381: interpolation() at its default level). */
+int lfsd_aux_solve_cubic(int dtype, int batch, int n_grid,
+                         const void* horizon, const void* auxvar, const void* consts, int const_per_traj,
+                         const void* state_grid, const void* control_grid, const void* costate_grid,
+                         const void* state_curv, const void* control_curv, const void* costate_curv,
+                         void* Z_grid,
+                         int n_waypoints, int n_iface, const int* iface_idx,
+                         const void* taus, const void* waypoints,
+                         void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                         int substeps, double rtol, int* stats,
+                         const int* oc_status, int skip_status_mask, void* stream);
+int lfsd_aux_riccati_cubic(int dtype, int batch, int n_grid,
+                           const void* horizon, const void* auxvar, const void* consts, int const_per_traj,
+                           const void* state_grid, const void* control_grid, const void* costate_grid,
+                           const void* state_curv, const void* control_curv, const void* costate_curv,
+                           void* Z_grid, int substeps, double rtol, int* stats,
+                           const int* oc_status, int skip_status_mask, void* stream);
+int lfsd_aux_forward_cubic(int dtype, int batch, int n_grid,
+                           const void* horizon, const void* auxvar, const void* consts, int const_per_traj,
+                           const void* state_grid, const void* control_grid, const void* costate_grid,
+                           const void* state_curv, const void* control_curv, const void* costate_curv,
+                           const void* Z_grid,
+                           int n_waypoints, int n_iface, const int* iface_idx,
+                           const void* taus, const void* waypoints,
+                           void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                           int substeps, double rtol, int* stats,
+                           const int* oc_status, int skip_status_mask, void* stream);
 
 /* theta <- update(theta, grad) for every trajectory; m/v/vhat are optimizer state [B][n_param]
  * (m: Nesterov velocity or first moment; v: second moment; vhat: AMSGrad max; unused ones may be NULL).

@@ -50,6 +50,7 @@ class COCSys:
         self.exact_after = 16            # iteration from which the exact stage Hessian is forced
         self.aux_dtype = None            # None: same as dtype; torch.float64: fp64 auxiliary (Riccati/sensitivity) pass
         self.mapping = "auto"            # "auto" | "lockstep" | "wide": mapping of the OC solve onto the machine
+        self.aux_interpolation = "linear"    # "linear": auxSysSolver takes linear interpolants only; "as_given": also the cubic one
         # state bounds (augmented Lagrangian): first penalty, its growth, feasibility tolerance (None: 1e-7 fp64 / 1e-4 fp32,
         # relative to 1 + the largest finite bound), limit of outer iterations
         self.state_rho0, self.state_rho_growth, self.state_tol, self.state_max_outer = 10.0, 10.0, None, 40
@@ -147,7 +148,12 @@ class COCSys:
         if aux_dtype is not None:
             self.aux_dtype = aux_dtype
 
-    def setSolverOptions(self, max_iter=None, tol=None, aux_substeps=None, exact_after=None, aux_rtol=None, mapping=None):
+    def setSolverOptions(self, max_iter=None, tol=None, aux_substeps=None, exact_after=None, aux_rtol=None, mapping=None,
+                         aux_interpolation=None):
+        """aux_interpolation: what ``auxSysSolver(time_grid, opt_sol, theta)`` accepts as ``opt_sol``.  "linear" (default): the linear
+        interpolant of its grid values only, anything else is refused.  "as_given": the reference's behaviour (CPDP.py:320-323, 347:
+        it integrates along whatever it is handed) for the two interpolants ``cocSolver`` can return -- also the cubic one of
+        ``interplation_level=2`` (scipy's not-a-knot spline, from ``interpolation(x, y, 2)`` or a user's own ``CubicSpline``)."""
         if max_iter is not None:
             self.max_iter = int(max_iter)
         if tol is not None:
@@ -162,6 +168,10 @@ class COCSys:
             if mapping not in runtime.MAPPINGS:
                 raise LfsdError("mapping must be one of %s" % sorted(runtime.MAPPINGS))
             self.mapping = mapping
+        if aux_interpolation is not None:
+            if aux_interpolation not in ("linear", "as_given"):
+                raise LfsdError("aux_interpolation must be 'linear' or 'as_given'")
+            self.aux_interpolation = aux_interpolation
 
     def use_library(self, path_or_lib):
         """Bind an already built model library (tests use this to inject the SIMT-emulator build)."""
@@ -374,8 +384,11 @@ class COCSys:
             raise ValueError("A value in taus is outside the interpolation range [0, horizon].")
 
     def auxSysSolverBatch(self, sol, taus=None, waypoints=None, interface_idx=None, auxvar=None, want_grids=False,
-                          Z_grid=None, out=None, phase_hook=None, validate=True, skip_status=None):
+                          Z_grid=None, out=None, phase_hook=None, validate=True, skip_status=None, interplation_level=1):
         """Differentiate the PMP along ``sol`` and (optionally) evaluate the sparse-waypoint loss + gradient.
+        ``interplation_level`` (the reference's spelling, CPDP.py:92): 1 -- along the linear interpolant of the solved grids, what
+        ``cocSolver`` returns by default; 2 -- along their cubic interpolant (``cocSolver(..., interplation_level=2)``, CPDP.py:388-390):
+        the curvature grids are fitted on the device (``lfsd_grid_curvature``) and the sweeps run the ``*_cubic`` entry points.
         ``skip_status``: OC-solve statuses whose rows are NOT differentiated (NaN loss / gradient, no sweep).  Default:
         FAILED (4) only -- a solve that ended with non-finite grids has nothing to differentiate and would otherwise hold
         the launch at the refinement cap; a solve at the iteration limit (3) is differentiated as the reference does,
@@ -406,7 +419,7 @@ class COCSys:
             skip_status = ()
         return lib.aux_solve(hz, th, cs, X, U, Lm, tt, wp, ii, substeps=self.aux_substeps, want_grids=want_grids,
                              Z_grid=Z_grid, out=out, phase_hook=phase_hook, rtol=self.aux_rtol, oc_status=status,
-                             skip_status=skip_status)
+                             skip_status=skip_status, interp_level=interplation_level)
 
     # ---- the reference's one-trajectory calls --------------------------------------------------------
     def cocSolver(self, ini_state, horizon, auxvar_value=1, interplation_level=1, print_level=0):
@@ -431,12 +444,14 @@ class COCSys:
         """CPDP.py:301-381: returns auxsys_sol(t) -> [vec(dx/dtheta) (n*p, row-major), vec(du/dtheta) (m*p)]."""
         lib = self.compile()
         n, m, p = lib.n_state, lib.n_control, lib.n_auxvar
-        # The reference integrates the auxiliary ODEs along WHATEVER interpolant it is handed (CPDP.py:320, 347); the sweeps here
-        # differentiate along the LINEAR interpolant of the grid values (interplation_level 1, what every example uses).  A cubic
-        # opt_sol (cocSolver(..., interplation_level=2), CPDP.py:388-390) would silently be resampled to that -- refuse it instead.
+        # The reference integrates the auxiliary ODEs along WHATEVER interpolant it is handed (CPDP.py:320, 347).  The sweeps here
+        # know two: the LINEAR interpolant of the grid values (interplation_level 1, what every example uses) and the CUBIC one of
+        # cocSolver(..., interplation_level=2) (CPDP.py:388-390: scipy's not-a-knot spline).  By default only the first is taken and a
+        # cubic opt_sol is refused -- it must not silently be resampled to the linear one; setSolverOptions(aux_interpolation=
+        # "as_given") differentiates along either.  Anything else is refused under both settings.
         # (interpolation() tags what it returns with `lfsd_level`; an interpolant from elsewhere is probed instead: a piecewise-linear
-        #  one is reproduced by the linear interpolant of its own grid values at the interval midpoints.  Nothing relies on scipy's
-        #  private attributes.)
+        #  one is reproduced by the linear interpolant of its own grid values at the interval midpoints, the not-a-knot spline by
+        #  that spline of its own grid values.  Nothing relies on scipy's private attributes.)
         level = getattr(opt_sol, "lfsd_level", None)
         if level is None:
             tg_ = np.asarray(time_grid, dtype=np.float64)
@@ -444,10 +459,22 @@ class COCSys:
             gv = np.asarray(opt_sol(tg_), dtype=np.float64)
             gm = np.asarray(opt_sol(mid), dtype=np.float64)
             lin = 0.5 * (gv[:-1] + gv[1:])
-            level = 1 if np.abs(gm - lin).max() <= 1e-9 * max(1.0, np.abs(gv).max()) else "non-linear"
-        if level != 1:
-            raise LfsdError("auxSysSolver: opt_sol is not the linear interpolant of its grid (interplation level %r); the HIP sweeps "
-                            "integrate along the linear interpolant (interplation_level=1, CPDP.py:386) only" % (level,))
+            thr = 1e-9 * max(1.0, np.abs(gv).max())
+            level = "unknown"
+            if np.abs(gm - lin).max() <= thr:
+                level = 1
+            elif len(tg_) >= 4 and np.abs(np.diff(tg_) - (tg_[-1] - tg_[0]) / (len(tg_) - 1)).max() <= 1e-9 * abs(tg_[-1] - tg_[0]):
+                c = notaknot_curvature(gv)
+                if np.abs(gm - (lin - 0.375 * (c[:-1] + c[1:]))).max() <= thr:      # ((1/2)^3 - 1/2 = -3/8 on both curvatures)
+                    level = 2
+        if level == 2 and self.aux_interpolation != "as_given":
+            raise LfsdError("auxSysSolver: opt_sol is the cubic interpolant of its grid (interplation level 2); by default the HIP sweeps "
+                            "take the linear interpolant (interplation_level=1, CPDP.py:386) only -- "
+                            "setSolverOptions(aux_interpolation='as_given') differentiates along the cubic one")
+        if level not in (1, 2):
+            raise LfsdError("auxSysSolver: opt_sol is neither the linear interpolant of its grid (interplation level 1, CPDP.py:386) nor "
+                            "its not-a-knot cubic spline (level 2, CPDP.py:388-390; needs setSolverOptions(aux_interpolation="
+                            "'as_given')): the HIP sweeps integrate along these two only (level %r)" % (level,))
         time_grid = np.asarray(time_grid, dtype=np.float64)
         N = len(time_grid) - 1
         g = np.asarray(opt_sol(time_grid), dtype=np.float64)
@@ -455,7 +482,7 @@ class COCSys:
         sol = dict(state_grid=self._t(g[None, :, 0:n]), control_grid=self._t(g[None, :, n:n + m]),
                    costate_grid=self._t(g[None, :, n + m:]), horizon=self._t([time_grid[-1] - time_grid[0]]),
                    auxvar=self._t(e[None, :]), consts=self.consts_tensor())
-        aux = self.auxSysSolverBatch(sol, want_grids=True)
+        aux = self.auxSysSolverBatch(sol, want_grids=True, interplation_level=level)
         self.last_aux = aux
         X = aux["auxX_grid"][0].double().cpu().numpy().transpose(0, 2, 1).reshape(N + 1, n * p)
         U = aux["auxU_grid"][0].double().cpu().numpy().transpose(0, 2, 1).reshape(N + 1, m * p)
@@ -469,8 +496,33 @@ class COCSys:
             f = ip.interp1d(x, y, axis=0, kind='cubic')
         else:
             return None                     # (the reference falls off the end of its ifs as well)
-        f.lfsd_level = method              # read by auxSysSolver: level 2 is returned, as in the reference, but not differentiated along
+        f.lfsd_level = method              # read by auxSysSolver (level 2 is differentiated along under aux_interpolation="as_given")
         return f
+
+
+def notaknot_curvature(y):
+    """Curvatures c_k = h^2 y''(t_k) / 6 of scipy's interp1d(kind='cubic') -- the not-a-knot cubic spline -- through the rows of
+    y [N+1, ...] on a uniform grid, N >= 3 (host restatement in fp64 of csrc/cpdp_spline.h; used to recognise such an interpolant).
+    With d_k = y_k-1 - 2 y_k + y_k+1:  c_1 = d_1 / 6, c_N-1 = d_N-1 / 6, the (1,4,1) system for c_2 .. c_N-2 between them, and
+    c_0 = 2 c_1 - c_2, c_N = 2 c_N-1 - c_N-2."""
+    y = np.asarray(y, dtype=np.float64)
+    N = y.shape[0] - 1
+    if N < 3:
+        raise LfsdError("the cubic interpolant needs n_grid >= 3 (four nodes)")
+    d = y[:-2] - 2.0 * y[1:-1] + y[2:]               # d[k-1] = d_k
+    c = np.zeros_like(y)
+    c[1], c[N - 1] = d[0] / 6.0, d[N - 2] / 6.0
+    if N >= 5:
+        A = np.diag(np.full(N - 3, 4.0)) + np.diag(np.ones(N - 4), 1) + np.diag(np.ones(N - 4), -1)
+        rhs = d[1:N - 2].copy()
+        rhs[0] = rhs[0] - c[1]
+        rhs[-1] = rhs[-1] - c[N - 1]
+        c[2:N - 1] = np.linalg.solve(A, rhs.reshape(N - 3, -1)).reshape(rhs.shape)
+    elif N == 4:
+        c[2] = (d[1] - c[1] - c[3]) / 4.0
+    c[0] = 2.0 * c[1] - c[2]
+    c[N] = 2.0 * c[N - 1] - c[N - 2]
+    return c
 
 
 class COCSys_TimeVarying(COCSys):
@@ -513,13 +565,20 @@ class SparseDemoLearner:
     took; 0 = still learning) and ``n_active`` report the state; ``step`` returns full-size (loss, grad) in which a stopped seed
     keeps its last values, and launches nothing once ``n_active == 0``.  A loop timed with the rule on pays that one host read per
     step.
+
+    ``interplation_level`` (the reference's spelling; default 1): 2 differentiates every step along the cubic interpolant of the
+    solved grids (``cocSolver(..., interplation_level=2)`` handed to ``auxSysSolver``, CPDP.py:388-390) instead of the linear one;
+    one more small launch per grid and step (``lfsd_grid_curvature``).  Every other option combines with it.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
-                 skip_unconverged=None, stop_rule=None):
+                 skip_unconverged=None, stop_rule=None, interplation_level=1):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
+        if interplation_level not in (1, 2):
+            raise LfsdError("interplation_level must be 1 (linear) or 2 (cubic), got %r" % (interplation_level,))
+        self.interplation_level = interplation_level
         self.b1, self.b2, self.eps = beta_1, beta_2, epsilon
         if method not in runtime.OPT_METHODS:
             raise Exception("Wrong optimization method type!")
@@ -625,7 +684,8 @@ class SparseDemoLearner:
         # status below): the diverged seeds of a fixed learning rate otherwise hold the Riccati launch 20x longer
         self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, Z_grid=self._Z,
                                               out=self._aux_out(), phase_hook=phase, validate=False,
-                                              skip_status=(3, 4) if self.skip_unconverged else None)
+                                              skip_status=(3, 4) if self.skip_unconverged else None,
+                                              interplation_level=self.interplation_level)
         self._Z = self._aux["Z_grid"]
         loss, grad = self._aux["loss"].to(self.theta.dtype), self._aux["grad"].to(self.theta.dtype)
         if self.skip_unconverged:
@@ -689,7 +749,8 @@ class SparseDemoLearner:
         phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
         aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, Z_grid=full["Z"][:n],
                                         out={k: full["aux"][k][:n] for k in ("loss", "grad", "stats")}, phase_hook=phase,
-                                        validate=False, skip_status=(3, 4) if self.skip_unconverged else None)
+                                        validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
+                                        interplation_level=self.interplation_level)
         self._sol_active, self._aux_active = sol, aux
         self._prev = (sol["control_grid"], sol["status"])
         loss, grad = aux["loss"].to(self.theta.dtype), aux["grad"].to(self.theta.dtype)

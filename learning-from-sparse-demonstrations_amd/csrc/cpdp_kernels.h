@@ -18,15 +18,19 @@
 //                         + getloss_*corrections      lib/QuadAlgorithm.py:616-673
 //   optimizer_kernel      Vanilla/Nesterov/Adam/Nadam/AMSGrad updates  lib/QuadAlgorithm.py:454-578
 //   stop_compact_kernel   the loop's stop test, per seed                lib/QuadAlgorithm.py:239-257
+//   grid_curvature_kernel COCSys.interpolation(x, y, 2)                 CPDP.py:388-390 (curvature grids of the cubic
+//                         interpolant; aux_*_cubic_kernel are the two sweeps along it)
 //
 // The same source builds for the GPU with hipcc and, with -DLFSD_EMU, for the CPU
 // SIMT emulator in tests/emu (test infrastructure; never used by the product path).
 //
 // Sources: cpdp_common.h (switches, primitives, dense helpers), cpdp_oc.h (OC solve), cpdp_aux.h (auxiliary
-// system sweeps + loss), cpdp_opt.h (update rules), cpdp_rows.h (per-seed stop rule, row compaction / gather / scatter).
+// system sweeps + loss), cpdp_opt.h (update rules), cpdp_rows.h (per-seed stop rule, row compaction / gather / scatter),
+// cpdp_spline.h (curvature fit of the cubic interpolant).
 #pragma once
 #include "cpdp_common.h"
 #include "cpdp_oc.h"
+#include "cpdp_spline.h"
 #include "cpdp_aux.h"
 #include "cpdp_opt.h"
 #include "cpdp_rows.h"

@@ -8,6 +8,7 @@
 #include <algorithm>
 #if !defined(LFSD_SPLIT_RICCATI)
 #include "lfsd_riccati.inc"
+#include "lfsd_cubic.inc"
 #endif
 
 LFSD_API int lfsd_get_model_info(lfsd_model_info* out) {
@@ -299,8 +300,12 @@ static int aux_phase_t(int phases, int batch, int n_grid, const void* horizon, c
                        int const_per_traj, const void* state_grid, const void* control_grid, const void* costate_grid,
                        void* Z_grid, int n_waypoints, int n_iface, const int* iface_idx, const void* taus,
                        const void* waypoints, void* loss, void* grad, void* auxX_grid, void* auxU_grid, int substeps,
-                       double rtol, int* stats, const int* oc_status, int skip_mask, void* stream) {
-  lfsd::AuxArgs<T> a;
+                       double rtol, int* stats, const int* oc_status, int skip_mask, void* stream,
+                       const void* state_curv = nullptr, const void* control_curv = nullptr, const void* costate_curv = nullptr) {
+  // (interpolation level 2 when the three curvature grids are given: the level-1 launches take the AuxArgs base, as ever)
+  lfsd::AuxArgsCubic<T> a;
+  const bool cubic = state_curv != nullptr;
+  a.state_curv = (const T*)state_curv; a.control_curv = (const T*)control_curv; a.costate_curv = (const T*)costate_curv;
   // rtol > 0: error-controlled sub-stepping from `substeps` (default 1) units per interval upwards;
   // rtol = 0: a fixed minimum of `substeps` (default 4) units, refined for stiffness only (the round-1 behaviour)
   a.batch = batch; a.n_grid = n_grid; a.substeps = substeps > 0 ? substeps : (rtol > 0 ? 1 : 4);
@@ -337,8 +342,8 @@ static int aux_phase_t(int phases, int batch, int n_grid, const void* horizon, c
   const unsigned grid = (unsigned)(((long long)batch + GPB - 1) / GPB);
   if (phases & 1) {
     int rc;
-    if constexpr (sizeof(T) == 4) rc = lfsd_detail::launch_riccati_f32(grid, stream, a);
-    else rc = lfsd_detail::launch_riccati_f64(grid, stream, a);
+    if constexpr (sizeof(T) == 4) rc = cubic ? lfsd_detail::launch_riccati_cubic_f32(grid, stream, a) : lfsd_detail::launch_riccati_f32(grid, stream, a);
+    else rc = cubic ? lfsd_detail::launch_riccati_cubic_f64(grid, stream, a) : lfsd_detail::launch_riccati_f64(grid, stream, a);
     if (rc) return rc;
   }
   if (phases & 2) {
@@ -346,7 +351,12 @@ static int aux_phase_t(int phases, int batch, int n_grid, const void* horizon, c
     constexpr int GF = lfsd::fwd_lanes<Model>() < G ? lfsd::fwd_lanes<Model>() : G;
     constexpr int GPBF = 64 / GF;
     const unsigned grid_f = (unsigned)(((long long)batch + GPBF - 1) / GPBF);
-    LFSD_LAUNCH((lfsd::aux_forward_kernel<Model, T, GF>), grid_f, 64, stream, a);
+    if (cubic) {
+      if constexpr (sizeof(T) == 4) return lfsd_detail::launch_forward_cubic_f32(grid_f, stream, a);
+      else return lfsd_detail::launch_forward_cubic_f64(grid_f, stream, a);
+    }
+    const lfsd::AuxArgs<T>& a1 = a;
+    LFSD_LAUNCH((lfsd::aux_forward_kernel<Model, T, GF>), grid_f, 64, stream, a1);
     return launch_status();
   }
   return 0;
@@ -357,7 +367,10 @@ static int aux_dispatch(int phases, int dtype, int batch, int n_grid, const void
                         const void* costate_grid, void* Z_grid, int n_waypoints, int n_iface, const int* iface_idx,
                         const void* taus, const void* waypoints, void* loss, void* grad, void* auxX_grid,
                         void* auxU_grid, int substeps, double rtol, int* stats, const int* oc_status, int skip_mask,
-                        void* stream) {
+                        void* stream, int level = 1, const void* state_curv = nullptr, const void* control_curv = nullptr,
+                        const void* costate_curv = nullptr) {
+  if (level == 2 && (!state_curv || !control_curv || !costate_curv || n_grid < 3)) return LFSD_EINVAL;      // (scipy's cubic needs four nodes)
+  if (level != 2) state_curv = control_curv = costate_curv = nullptr;
   if (batch <= 0 || n_grid <= 0 || n_waypoints < 0 || n_iface < 0 || substeps < 0 || !(rtol >= 0)) return LFSD_EINVAL;
   if (!horizon || !auxvar || !state_grid || !control_grid || !costate_grid || !Z_grid) return LFSD_EINVAL;
   if ((phases & 2) && (!loss || !grad)) return LFSD_EINVAL;
@@ -369,11 +382,13 @@ static int aux_dispatch(int phases, int dtype, int batch, int n_grid, const void
   if (dtype == LFSD_F32)
     return aux_phase_t<float>(phases, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
                               costate_grid, Z_grid, n_waypoints, n_iface, iface_idx, taus, waypoints, loss, grad,
-                              auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream);
+                              auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream, state_curv, control_curv,
+                              costate_curv);
   if (dtype == LFSD_F64)
     return aux_phase_t<double>(phases, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid,
                                control_grid, costate_grid, Z_grid, n_waypoints, n_iface, iface_idx, taus, waypoints,
-                               loss, grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream);
+                               loss, grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream, state_curv,
+                               control_curv, costate_curv);
   return LFSD_EINVAL;
 }
 
@@ -529,4 +544,50 @@ LFSD_API int lfsd_gather_rows(int n_rows, long long row_bytes, const int* index,
 
 LFSD_API int lfsd_scatter_rows(int n_rows, long long row_bytes, const int* index, const void* src, void* dst, void* stream) {
   return copy_rows_launch(true, n_rows, row_bytes, index, src, dst, stream);
+}
+
+// ---- interpolation level 2 (ABI 11): the same three calls along the cubic interpolant of the grids (CPDP.py:388-390) ----
+LFSD_API int lfsd_aux_solve_cubic(int dtype, int batch, int n_grid, const void* horizon, const void* auxvar,
+                                  const void* consts, int const_per_traj, const void* state_grid, const void* control_grid,
+                                  const void* costate_grid, const void* state_curv, const void* control_curv,
+                                  const void* costate_curv, void* Z_grid, int n_waypoints, int n_iface,
+                                  const int* iface_idx, const void* taus, const void* waypoints, void* loss, void* grad,
+                                  void* auxX_grid, void* auxU_grid, int substeps, double rtol, int* stats,
+                                  const int* oc_status, int skip_status_mask, void* stream) {
+  return aux_dispatch(3, dtype, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
+                      costate_grid, Z_grid, n_waypoints, n_iface, iface_idx, taus, waypoints, loss, grad, auxX_grid,
+                      auxU_grid, substeps, rtol, stats, oc_status, skip_status_mask, stream, 2, state_curv, control_curv,
+                      costate_curv);
+}
+
+LFSD_API int lfsd_aux_riccati_cubic(int dtype, int batch, int n_grid, const void* horizon, const void* auxvar,
+                                    const void* consts, int const_per_traj, const void* state_grid,
+                                    const void* control_grid, const void* costate_grid, const void* state_curv,
+                                    const void* control_curv, const void* costate_curv, void* Z_grid, int substeps,
+                                    double rtol, int* stats, const int* oc_status, int skip_status_mask, void* stream) {
+  return aux_dispatch(1, dtype, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
+                      costate_grid, Z_grid, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      substeps, rtol, stats, oc_status, skip_status_mask, stream, 2, state_curv, control_curv, costate_curv);
+}
+
+LFSD_API int lfsd_aux_forward_cubic(int dtype, int batch, int n_grid, const void* horizon, const void* auxvar,
+                                    const void* consts, int const_per_traj, const void* state_grid,
+                                    const void* control_grid, const void* costate_grid, const void* state_curv,
+                                    const void* control_curv, const void* costate_curv, const void* Z_grid,
+                                    int n_waypoints, int n_iface, const int* iface_idx, const void* taus,
+                                    const void* waypoints, void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                                    int substeps, double rtol, int* stats, const int* oc_status, int skip_status_mask,
+                                    void* stream) {
+  return aux_dispatch(2, dtype, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
+                      costate_grid, const_cast<void*>(Z_grid), n_waypoints, n_iface, iface_idx, taus, waypoints, loss,
+                      grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_status_mask, stream, 2, state_curv,
+                      control_curv, costate_curv);
+}
+
+// curvature grids of the not-a-knot cubic spline through each component of a grid (cpdp_spline.h)
+LFSD_API int lfsd_grid_curvature(int dtype, int batch, int n_grid, int n_comp, const void* grid, void* curv, void* stream) {
+  if (batch <= 0 || n_grid < 3 || n_comp <= 0 || !grid || !curv || grid == curv) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) return lfsd_detail::launch_grid_curvature_f32(batch, n_grid, n_comp, (const float*)grid, (float*)curv, stream);
+  if (dtype == LFSD_F64) return lfsd_detail::launch_grid_curvature_f64(batch, n_grid, n_comp, (const double*)grid, (double*)curv, stream);
+  return LFSD_EINVAL;
 }

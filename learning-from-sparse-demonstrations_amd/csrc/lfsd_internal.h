@@ -64,4 +64,11 @@ static int device_cu_count() {
 namespace lfsd_detail {
 int launch_riccati_f32(unsigned grid, void* stream, const lfsd::AuxArgs<float>& a);
 int launch_riccati_f64(unsigned grid, void* stream, const lfsd::AuxArgs<double>& a);
+// interpolation level 2 (lfsd_cubic.inc: a third unit of the product build)
+int launch_riccati_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCubic<float>& a);
+int launch_riccati_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a);
+int launch_forward_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCubic<float>& a);
+int launch_forward_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a);
+int launch_grid_curvature_f32(int batch, int n_grid, int n_comp, const float* grid, float* curv, void* stream);
+int launch_grid_curvature_f64(int batch, int n_grid, int n_comp, const double* grid, double* curv, void* stream);
 }

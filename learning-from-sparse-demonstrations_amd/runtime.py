@@ -87,22 +87,27 @@ def _hipcc_flags(spec, extra=()):
 # of a join block, which a third wrong build showed under the DEFAULT one -- and every build is now scanned for it (_checked_build below).
 TUNED_CAPI = ()
 TUNED_RICCATI = ()
+TUNED_CUBIC = ()
+UNITS = ("capi", "riccati", "cubic")
 
 
-def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUNED_RICCATI):
-    """Product build: two translation units -- the Riccati sweep apart from everything else -- so that each gets the
-    compiler settings it measured best with (csrc/lfsd_internal.h, profiles/r01_tune_compiler_flags.txt), then the link.
-    Both are compiled without clang's SLP vectoriser."""
+def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUNED_RICCATI, extra_cubic=TUNED_CUBIC):
+    """Product build: three translation units (UNITS) -- the Riccati sweep apart from everything else, so that each gets the
+    compiler settings it measured best with (csrc/lfsd_internal.h, profiles/r01_tune_compiler_flags.txt), and the kernels of
+    interpolation level 2 apart from both, so that the device code of the first two is what it was without them (csrc/
+    lfsd_cubic.inc) -- then the link.  All are compiled without clang's SLP vectoriser.  Returns (one command per unit + the
+    link command, the object files)."""
     flags = _hipcc_flags(spec, extra) + ["-fno-slp-vectorize"]
-    o1, o2 = out + ".capi.o", out + ".riccati.o"
+    o1, o2, o3 = out + ".capi.o", out + ".riccati.o", out + ".cubic.o"
     return ([flags + ["-c", "-DLFSD_SPLIT_RICCATI", os.path.join(CSRC_DIR, "lfsd_capi.cpp"), "-o", o1] + list(extra_capi),
              flags + ["-c", os.path.join(CSRC_DIR, "lfsd_riccati.cpp"), "-o", o2] + list(extra_riccati),
-             [find_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", o1, o2, "-o", out]], [o1, o2])
+             flags + ["-c", os.path.join(CSRC_DIR, "lfsd_cubic.cpp"), "-o", o3] + list(extra_cubic),
+             [find_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", o1, o2, o3, "-o", out]], [o1, o2, o3])
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "lfsd_capi.cpp", "lfsd_internal.h",
-                  "lfsd_riccati.inc", "lfsd_riccati.cpp")
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+                  "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
 # Every build is compiled with -save-temps and its gfx950 assembly scanned by lfsd_amd.isa_check (VGPR spills placed before the
@@ -120,7 +125,7 @@ def isa_record_path(lib_path):
 
 
 def isa_record_clean(lib_path):
-    """The library was built by _checked_build of this version and both units passed (a library without such a record -- built by an
+    """The library was built by _checked_build of this version and every unit passed (a library without such a record -- built by an
     older tree or by hand -- counts as stale: build_library compiles it again)."""
     import json
     try:
@@ -128,7 +133,7 @@ def isa_record_clean(lib_path):
     except (OSError, ValueError):
         return False
     units = rec.get("units", {})
-    return rec.get("isa_check") == ISA_CHECK_VERSION and set(units) == {"capi", "riccati"} and all(u.get("hazards") == 0 for u in units.values()) \
+    return rec.get("isa_check") == ISA_CHECK_VERSION and set(units) == set(UNITS) and all(u.get("hazards") == 0 for u in units.values()) \
         and rec.get("sha256") == _sha256(lib_path)      # (the record belongs to THIS file, not to one a later hand build replaced)
 
 
@@ -142,7 +147,7 @@ def _sha256(path):
 
 
 def _checked_build(spec, out, extra=(), verbose=False, what="model"):
-    """Compile the two translation units into `out` (csrc/build/...), each with the first entry of SCHEDULE_ALTERNATES whose device
+    """Compile the translation units (UNITS) into `out` (csrc/build/...), each with the first entry of SCHEDULE_ALTERNATES whose device
     assembly passes isa_check; writes `<out>.isa.json` (what was scanned, which flags each unit was built with).  Raises LfsdError."""
     import json, shutil, tempfile
     from . import isa_check
@@ -152,13 +157,13 @@ def _checked_build(spec, out, extra=(), verbose=False, what="model"):
         tmp = os.path.join(work, "lib.so")
         record = {"isa_check": ISA_CHECK_VERSION, "units": {}}
         objs = []
-        for unit in ("capi", "riccati"):
-            tuned = TUNED_CAPI if unit == "capi" else TUNED_RICCATI
+        for ui, unit in enumerate(UNITS):
+            tuned = (TUNED_CAPI, TUNED_RICCATI, TUNED_CUBIC)[ui]
             tried, built = [], False
             for alt in SCHEDULE_ALTERNATES:
-                kw = {"extra_capi": tuple(tuned) + tuple(alt)} if unit == "capi" else {"extra_riccati": tuple(tuned) + tuple(alt)}
+                kw = {"extra_" + unit: tuple(tuned) + tuple(alt)}
                 cmds, obj_paths = hipcc_commands(spec, tmp, list(extra), **kw)
-                cmd = cmds[0 if unit == "capi" else 1] + ["-save-temps=obj"]
+                cmd = cmds[ui] + ["-save-temps=obj"]
                 if verbose:
                     print(" ".join(cmd))
                 for f in os.listdir(work):      # (the temporaries of the previous attempt)
@@ -181,13 +186,13 @@ def _checked_build(spec, out, extra=(), verbose=False, what="model"):
                         print("isa_check: %d spill(s) before an exec restore in %s (%s, flags %s): %s" % (len(hz), spec.name, unit, list(alt), hz[0]))
                     continue
                 record["units"][unit] = dict(isa_check.summary(text), flags=list(tuned) + list(alt), hazards=0, rejected=tried)
-                objs.append(obj_paths[0 if unit == "capi" else 1])
+                objs.append(obj_paths[ui])
                 built = True
                 break
             if not built:
                 raise LfsdError("every build of %s %s (%s) has VGPR spills before an exec restore (lfsd_amd/isa_check.py): %s"
                                 % (what, spec.name, unit, tried))
-        link = hipcc_commands(spec, tmp, list(extra))[0][2]
+        link = hipcc_commands(spec, tmp, list(extra))[0][-1]
         r = subprocess.run(link, cwd=CSRC_DIR, capture_output=True, text=True)
         if r.returncode != 0:
             raise LfsdError("link failed for %s %s:\n%s" % (what, spec.name, r.stderr[-3000:]))
@@ -267,7 +272,8 @@ class ModelLibrary:
 
     EXPORTS = ("lfsd_get_model_info", "lfsd_interface_dim", "lfsd_const_default", "lfsd_coc_workspace_bytes", "lfsd_coc_solve",
                "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
-               "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows")
+               "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
+               "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -292,6 +298,12 @@ class ModelLibrary:
         L.lfsd_aux_riccati.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, cd, vp, vp, ci, vp]
         L.lfsd_aux_forward.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp,
                                        ci, cd, vp, vp, ci, vp]
+        L.lfsd_grid_curvature.argtypes = [ci, ci, ci, ci, vp, vp, vp]
+        L.lfsd_aux_solve_cubic.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp,
+                                           ci, cd, vp, vp, ci, vp]
+        L.lfsd_aux_riccati_cubic.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, cd, vp, vp, ci, vp]
+        L.lfsd_aux_forward_cubic.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp,
+                                             ci, cd, vp, vp, ci, vp]
         L.lfsd_optimizer_step.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_lookahead.argtypes = [ci, ctypes.c_longlong, cd, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
@@ -299,7 +311,7 @@ class ModelLibrary:
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 10:
+        if rc != 0 or info.abi_version != 11:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -414,10 +426,34 @@ class ModelLibrary:
         out["workspace"] = workspace
         return out
 
+    def grid_curvature(self, grid, out=None):
+        """Curvature grid c_k = h^2 y''(t_k) / 6 of the not-a-knot cubic spline (scipy's interp1d(kind='cubic'), CPDP.py:388-390)
+        through every component of ``grid`` [B, n_grid+1, n_comp] (include/lfsd_cpdp.h, ABI 11); n_grid >= 3."""
+        if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+            raise LfsdError("grid must be a [B, n_grid+1, n_comp] tensor")
+        if grid.dtype not in _DT:
+            raise LfsdError("grid has dtype %s: float32 or float64" % grid.dtype)
+        B, N1, C = grid.shape
+        self._check(grid, (B, N1, C), grid.dtype, "grid")
+        if N1 < 4:
+            raise LfsdError("the cubic interpolant needs n_grid >= 3 (four nodes), got n_grid = %d" % (N1 - 1))
+        if out is None:
+            out = torch.empty_like(grid)
+        self._check(out, (B, N1, C), grid.dtype, "out")
+        if out.data_ptr() == grid.data_ptr():
+            raise LfsdError("grid_curvature does not run in place")
+        with self._on(grid):
+            rc = self.lib.lfsd_grid_curvature(_DT[grid.dtype], B, N1 - 1, C, self._p(grid), self._p(out), self._stream(grid))
+        self._rc(rc, "lfsd_grid_curvature")
+        return out
+
     def aux_solve(self, horizon, auxvar, consts, state_grid, control_grid, costate_grid, taus, waypoints, iface_idx,
                   substeps=0, want_grids=False, Z_grid=None, out=None, phase_hook=None, rtol=1e-3, oc_status=None,
-                  skip_status=()):
-        """``phase_hook(name)``, if given, is called before/after each of the two launches
+                  skip_status=(), interp_level=1, curvature=None):
+        """``interp_level`` 1: the sweeps differentiate along the linear interpolant of the grids (CPDP.py:386); 2: along their cubic
+        interpolant (CPDP.py:388-390; the ``*_cubic`` entry points).  ``curvature``: at level 2, the (state, control, costate)
+        curvature tensors if the caller has them (``grid_curvature``); fitted here otherwise; returned as ``out["curvature"]``.
+        ``phase_hook(name)``, if given, is called before/after each of the two launches
         ("riccati", "forward") so a caller can bracket them with HIP events (bench.py).
         ``oc_status`` [B] int32 (the status the OC solve wrote) + ``skip_status`` (status values, e.g. (3, 4)): rows with
         one of these statuses are not differentiated -- NaN loss / gradient, no sweep (include/lfsd_cpdp.h, ABI 8)."""
@@ -467,27 +503,46 @@ class ModelLibrary:
             skip_mask |= 1 << int(st)
         if skip_mask or oc_status is not None:      # (without a mask the status still tells the sweeps which rows to budget)
             self._check(oc_status, (B,), torch.int32, "oc_status")
+        if interp_level not in (1, 2):
+            raise LfsdError("interp_level must be 1 (linear) or 2 (cubic), got %r" % (interp_level,))
+        curv = ()
+        if interp_level == 2:
+            if N < 3:
+                raise LfsdError("the cubic interpolant needs n_grid >= 3 (four nodes), got n_grid = %d" % N)
+            grids = (state_grid, control_grid, costate_grid)
+            if curvature is None:
+                curvature = tuple(self.grid_curvature(g) for g in grids)
+            if len(curvature) != 3:
+                raise LfsdError("curvature is the triple (state, control, costate)")
+            for g, c, nm in zip(grids, curvature, ("state_curv", "control_curv", "costate_curv")):
+                self._check(c, tuple(g.shape), dt, nm)
+            curv = tuple(self._p(c) for c in curvature)
+        elif curvature is not None:
+            raise LfsdError("curvature tensors belong to interp_level=2")
+        sfx = "_cubic" if interp_level == 2 else ""
         auxX = auxU = None
         if want_grids:
             auxX = torch.empty((B, N + 1, p, n), dtype=dt, device=dev)
             auxU = torch.empty((B, N + 1, p, m), dtype=dt, device=dev)
         common = (_DT[dt], B, N, self._p(horizon), self._p(auxvar), self._p(consts), per_traj,
-                  self._p(state_grid), self._p(control_grid), self._p(costate_grid), self._p(Z_grid))
+                  self._p(state_grid), self._p(control_grid), self._p(costate_grid)) + curv + (self._p(Z_grid),)
         tail = (nw, ni, self._p(iface_idx), self._p(taus), self._p(waypoints), self._p(out["loss"]),
                 self._p(out["grad"]), self._p(auxX), self._p(auxU), int(substeps), float(rtol), self._p(out["stats"]),
                 self._p(oc_status), skip_mask, self._stream(state_grid))
         with self._on(state_grid):
             if phase_hook is None:
-                self._rc(self.lib.lfsd_aux_solve(*common, *tail), "lfsd_aux_solve")
+                self._rc(getattr(self.lib, "lfsd_aux_solve" + sfx)(*common, *tail), "lfsd_aux_solve" + sfx)
             else:
                 phase_hook("riccati")
-                self._rc(self.lib.lfsd_aux_riccati(*common, int(substeps), float(rtol), self._p(out["stats"]),
-                                                   self._p(oc_status), skip_mask, self._stream(state_grid)), "lfsd_aux_riccati")
+                self._rc(getattr(self.lib, "lfsd_aux_riccati" + sfx)(*common, int(substeps), float(rtol), self._p(out["stats"]),
+                                                                     self._p(oc_status), skip_mask, self._stream(state_grid)),
+                         "lfsd_aux_riccati" + sfx)
                 phase_hook("forward")
-                self._rc(self.lib.lfsd_aux_forward(*common, *tail), "lfsd_aux_forward")
+                self._rc(getattr(self.lib, "lfsd_aux_forward" + sfx)(*common, *tail), "lfsd_aux_forward" + sfx)
                 phase_hook("end")
         out["Z_grid"] = Z_grid
         out["auxX_grid"], out["auxU_grid"] = auxX, auxU
+        out["curvature"] = curvature if interp_level == 2 else None
         return out
 
     def optimizer_step(self, method, theta, grad, iter_idx, lr, mu=0.9, beta1=0.9, beta2=0.999, eps=1e-8, m=None,

@@ -1,4 +1,4 @@
-"""Device assembly of a model library's two translation units (no GPU needed).
+"""Device assembly of a model library's translation units (no GPU needed).
 usage: isa_dump.py <model> <outdir> [extra hipcc flags...]   ->  <outdir>/<model>_capi.s, <model>_riccati.s
 Prints, per kernel, the count of a few instruction classes (s_barrier, v_mfma, scratch, ds_*, v_pk_*)."""
 import os, re, subprocess, sys
@@ -12,7 +12,7 @@ oc, _, _ = models.ZOO[kind]()
 spec = oc.model_spec()
 runtime.write_header(spec)
 cmds, objs = runtime.hipcc_commands(spec, "/tmp/isa_%s.so" % spec.hash(), extra=extra)
-for cmd, unit in zip(cmds[:2], ("capi", "riccati")):
+for cmd, unit in zip(cmds[:-1], runtime.UNITS):
     out = os.path.join(outdir, "%s_%s.s" % (kind, unit))
     c = [a for a in cmd if a != "-c"]
     c[c.index("-o") + 1] = out

@@ -17,7 +17,7 @@ oc, _, _ = models.ZOO[kind]()
 spec = oc.model_spec()
 runtime.write_header(spec)
 cmds, objs = runtime.hipcc_commands(spec, "/tmp/kres_%s.so" % spec.hash(), extra=["-Rpass-analysis=kernel-resource-usage"] + extra)
-for cmd in cmds[:2]:
+for cmd in cmds[:-1]:
     r = subprocess.run(cmd, cwd=runtime.CSRC_DIR, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     name = None
