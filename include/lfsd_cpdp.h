@@ -21,6 +21,10 @@
  *   lfsd_gather_rows / lfsd_scatter_rows   the dense batch of the seeds still learning (ABI 10)
  *   lfsd_grid_curvature   CPDP/CPDP.py:388-390  COCSys.interpolation(x, y, 2): the cubic interpolant of a grid (ABI 11)
  *   lfsd_aux_*_cubic      CPDP/CPDP.py:301-381  auxSysSolver handed that interpolant (interplation_level=2; ABI 11)
+ *   lfsd_sample_grid      CPDP/CPDP.py:386-390  calling opt_sol(t) / auxsys_sol(t): Examples/rocket_groundtruth.py:75-84
+ *                         true_opt_sol(taus), lib/QuadAlgorithm.py:306-317 opt_sol(linspace(0, T, 101)) (ABI 12)
+ *   lfsd_waypoint_vjp     the `diff_loss += r @ auxsys_sol(tau)` of a user-written loss: Examples/pendulum_timewarping.py:72-86,
+ *                         Examples/rocket_groundtruth.py:45-70, lib/QuadAlgorithm.py:616-673 (ABI 12)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -29,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 11
+#define LFSD_ABI_VERSION 12
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -229,6 +233,37 @@ int lfsd_aux_forward_cubic(int dtype, int batch, int n_grid,
                            void* loss, void* grad, void* auxX_grid, void* auxU_grid,
                            int substeps, double rtol, int* stats,
                            const int* oc_status, int skip_status_mask, void* stream);
+
+/* ABI 12 -- user-defined losses.  Every example of the reference ends in a loss the user writes from two callables, opt_sol(t) ->
+ * [x, u, lambda] of cocSolver and auxsys_sol(t) -> [dx/dtheta, du/dtheta] of auxSysSolver (Examples/pendulum_timewarping.py:72-86,
+ * Examples/rocket_groundtruth.py:45-70, lib/QuadAlgorithm.py:616-673), and samples trajectories with the same callables
+ * (rocket_groundtruth.py:75-84, QuadAlgorithm.py:306-317).  lfsd_sample_grid is the batched call of such an interpolant:
+ *   grid [B][n_grid+1][n_comp]; curv: NULL -- the linear interpolant (CPDP.py:386) -- or the curvature grid lfsd_grid_curvature
+ *   fitted to `grid` -- the not-a-knot cubic (CPDP.py:388-390; then n_grid >= 3); horizon [B];
+ *   times [B][n_times] (times_per_traj = 1) or [n_times] shared by the batch (0);   out [B][n_times][n_comp].
+ * Interval and fraction as in the fused waypoint loss of lfsd_aux_solve: h = horizon / n_grid, k = clamp(floor(t / h), 0, n_grid-1),
+ * s = (t - k h) / h, y = y_k + s (y_k+1 - y_k) [+ ((1-s)^3 - (1-s)) c_k + (s^3 - s) c_k+1].  t = horizon is interval n_grid-1 at
+ * s = 1; a t outside [0, horizon] extrapolates its end interval (scipy raises ValueError: that check is the caller's); a NaN time
+ * gives a NaN row.  n_comp = n_state serves a state grid, n_comp = n_auxvar * n_state an auxX_grid.  Nothing of the model enters.
+ * LFSD_EINVAL: a NULL grid / horizon / times / out, batch / n_comp / n_times <= 0, n_grid < 1 (< 3 with curv), times_per_traj
+ * not 0 / 1, `out` overlapping an input, an unknown dtype, more than 2^31-1 workgroups. */
+int lfsd_sample_grid(int dtype, int batch, int n_grid, int n_comp, int n_times, int times_per_traj,
+                     const void* grid, const void* curv, const void* horizon, const void* times, void* out, void* stream);
+
+/* The chain rule of a loss L(x(tau_1..K), u(tau_1..K)) through auxsys_sol, without materialising auxsys_sol(tau):
+ *   grad[b][q] = sum_k ( sum_i rx[b][k][i] X(tau_k)[q][i]  +  sum_j ru[b][k][j] U(tau_k)[q][j] )
+ *   rx [B][K][n_state] = dL/dx(tau_k), ru [B][K][n_control] = dL/du(tau_k) (the caller's: autograd of a torch function, say);
+ *   X, U: the LINEAR interpolants of auxX_grid [B][n_grid+1][n_param][n_state], auxU_grid [B][n_grid+1][n_param][n_control] as
+ *   lfsd_aux_solve returns them (auxsys_sol is linear at either interpolation level, CPDP.py:381); interval rule as above;
+ *   horizon [B], taus [B][K], grad [B][n_param].  ru and auxU_grid: both or neither (a loss without a control term).
+ * Summed in a fixed order (k ascending, states then controls, components ascending), no atomics: a row's gradient is the same
+ * bits in any batch.  With rx = x(tau) - waypoint on the interface components this is the gradient lfsd_aux_solve fuses (its
+ * "no factor 2" convention, lib/QuadAlgorithm.py:630-637, is HALF the derivative of the squared distance).
+ * LFSD_EINVAL: a NULL required pointer, a non-positive size, n_grid < 1, exactly one of ru / auxU_grid, `grad` overlapping an
+ * input, an unknown dtype, more than 2^31-1 workgroups. */
+int lfsd_waypoint_vjp(int dtype, int batch, int n_grid, int n_state, int n_control, int n_param, int n_waypoints,
+                      const void* horizon, const void* taus, const void* rx, const void* ru,
+                      const void* auxX_grid, const void* auxU_grid, void* grad, void* stream);
 
 /* theta <- update(theta, grad) for every trajectory; m/v/vhat are optimizer state [B][n_param]
  * (m: Nesterov velocity or first moment; v: second moment; vhat: AMSGrad max; unused ones may be NULL).

@@ -377,6 +377,11 @@ class COCSys:
             idx = [int(i) for i in interface_idx]
             if any(i < 0 or i >= lib.n_state for i in idx):
                 raise LfsdError("interface_idx %s outside [0, n_state=%d)" % (idx, lib.n_state))
+        self.check_time_range(taus, horizon)
+
+    @staticmethod
+    def check_time_range(taus, horizon):
+        """scipy's interp1d raises ValueError for t outside [0, horizon] (CPDP.py:386); the kernels extrapolate: the check is here."""
         tt = torch.as_tensor(taus, dtype=torch.float64).cpu() if not isinstance(taus, torch.Tensor) else taus.double().cpu()
         hz = torch.as_tensor(horizon, dtype=torch.float64).cpu() if not isinstance(horizon, torch.Tensor) else horizon.double().cpu()
         hz = hz.reshape(-1, 1) if (hz.dim() >= 1 and tt.dim() == 2 and hz.numel() == tt.shape[0]) else hz.min()
@@ -420,6 +425,59 @@ class COCSys:
         return lib.aux_solve(hz, th, cs, X, U, Lm, tt, wp, ii, substeps=self.aux_substeps, want_grids=want_grids,
                              Z_grid=Z_grid, out=out, phase_hook=phase_hook, rtol=self.aux_rtol, oc_status=status,
                              skip_status=skip_status, interp_level=interplation_level)
+
+    def _times(self, times, dtype, batch):
+        tt = times if isinstance(times, torch.Tensor) else torch.as_tensor(np.asarray(times, dtype=np.float64))
+        tt = tt.to(device=self._dev(), dtype=dtype)
+        if tt.dim() == 0:
+            tt = tt.reshape(1)
+        if tt.dim() not in (1, 2) or (tt.dim() == 2 and tt.shape[0] != batch):
+            raise LfsdError("times must be [K] (shared by the batch) or [B, K], got %s" % (tuple(tt.shape),))
+        return tt.contiguous()
+
+    def sampleBatch(self, sol, times, interplation_level=1, validate=True):
+        """``opt_sol(times)`` of every trajectory of ``sol`` (cocSolverBatch), on the device: what the reference's examples call to make
+        demonstrations and final trajectories (Examples/rocket_groundtruth.py:75-84, lib/QuadAlgorithm.py:306-317) and inside their
+        loss functions.  times [K] (shared) or [B, K] -> dict(state [B,K,n], control [B,K,m], costate [B,K,n]).
+        ``interplation_level`` 1: the linear interpolant of the grids (CPDP.py:386); 2: their cubic one (CPDP.py:388-390) -- the
+        curvature grids are taken from ``sol["curvature"]`` (state, control, costate) if present, else fitted (``lfsd_grid_curvature``).
+        ``validate``: times outside [0, horizon] raise ValueError as scipy's interp1d does (a device->host read); without it
+        they extrapolate the end interval."""
+        lib = self.compile()
+        if interplation_level not in (1, 2):
+            raise LfsdError("interplation_level must be 1 (linear) or 2 (cubic), got %r" % (interplation_level,))
+        grids = (sol["state_grid"], sol["control_grid"], sol["costate_grid"])
+        dt, B = grids[0].dtype, grids[0].shape[0]
+        hz = sol["horizon"].to(dt)
+        tt = self._times(times, dt, B)
+        if validate:
+            self.check_time_range(tt, hz)
+        curv = (None, None, None)
+        if interplation_level == 2:
+            curv = sol.get("curvature")
+            if curv is None or any(c.dtype != dt for c in curv):
+                curv = tuple(lib.grid_curvature(g) for g in grids)
+        return {k: lib.sample_grid(g, hz, tt, curv=c) for k, g, c in zip(("state", "control", "costate"), grids, curv)}
+
+    def sampleAuxBatch(self, aux, horizon, times, validate=True):
+        """``auxsys_sol(times)`` of every trajectory of ``aux`` (auxSysSolverBatch(..., want_grids=True)), on the device:
+        dict(dx [B,K,p,n] = dx/dtheta, du [B,K,p,m] = du/dtheta), parameter-major as the grids are (the reference's vector is the
+        [n][p] row-major transpose, CPDP.py:352-381).  Linear at either interpolation level, as the reference's (CPDP.py:381)."""
+        lib = self.compile()
+        aX, aU = aux.get("auxX_grid"), aux.get("auxU_grid")
+        if aX is None or aU is None:
+            raise LfsdError("sampleAuxBatch needs the sensitivity grids: auxSysSolverBatch(..., want_grids=True)")
+        B, N1, p, n = aX.shape
+        m = aU.shape[3]
+        dt = aX.dtype
+        hz = self._t(horizon).to(dt)
+        hz = hz.expand(B).contiguous() if hz.dim() == 0 else hz
+        tt = self._times(times, dt, B)
+        if validate:
+            self.check_time_range(tt, hz)
+        K = tt.shape[-1]
+        return dict(dx=lib.sample_grid(aX.reshape(B, N1, p * n), hz, tt).reshape(B, K, p, n),
+                    du=lib.sample_grid(aU.reshape(B, N1, p * m), hz, tt).reshape(B, K, p, m))
 
     # ---- the reference's one-trajectory calls --------------------------------------------------------
     def cocSolver(self, ini_state, horizon, auxvar_value=1, interplation_level=1, print_level=0):
@@ -569,13 +627,33 @@ class SparseDemoLearner:
     ``interplation_level`` (the reference's spelling; default 1): 2 differentiates every step along the cubic interpolant of the
     solved grids (``cocSolver(..., interplation_level=2)`` handed to ``auxSysSolver``, CPDP.py:388-390) instead of the linear one;
     one more small launch per grid and step (``lfsd_grid_curvature``).  Every other option combines with it.
+
+    ``loss_fn`` (default ``None`` = the fused waypoint loss above, launch for launch): a user-written loss, as every example of the
+    reference ends in one (Examples/pendulum_timewarping.py:72-86, rocket_groundtruth.py:45-70, lib/QuadAlgorithm.py:616-673).
+    ``loss_fn(x_tau [B,K,n], u_tau [B,K,m]) -> loss [B]`` is any differentiable torch function of the states and controls at the
+    learner's ``taus`` (weights, ragged demonstrations as masks, Huber or geodesic distances, control terms; targets are its own
+    business: ``waypoints`` and ``interface_idx`` may be ``None``).  Per evaluation: the solve; the two sweeps with the sensitivity
+    grids written and no waypoints; ``sampleBatch`` at ``taus`` on the interpolant of ``interplation_level``; ``loss_fn`` under
+    autograd, which yields dL/dx(tau_k), dL/du(tau_k); ``lfsd_waypoint_vjp`` contracts them with the linear interpolants of the
+    sensitivity grids (``auxsys_sol`` is linear at either level, CPDP.py:381); the gradient is multiplied by ``grad_scale``.
+    ``grad_scale=1`` is the true derivative of ``loss_fn``.  The fused loss follows the reference's "no factor 2" convention
+    (lib/QuadAlgorithm.py:630-637: loss |r|^2, gradient r . dx/dtheta): it is ``loss_fn = ((x_tau[:, :, idx] - wp) ** 2).sum((1, 2))``
+    with ``grad_scale=0.5``.  It combines with both modes, ``warm_start``, ``skip_unconverged`` (a skipped row's grids are NaN, so are
+    its loss and gradient, and ``mask_unconverged`` freezes it), ``true_loss_print_flag`` and both interpolation levels.  Together
+    with ``stop_rule`` it is refused for now: the dense batch of the seeds still learning would have to hand ``loss_fn`` its row ids.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
-                 skip_unconverged=None, stop_rule=None, interplation_level=1):
+                 skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
+        if loss_fn is not None and not callable(loss_fn):
+            raise LfsdError("loss_fn must be callable: loss_fn(x_tau [B,K,n], u_tau [B,K,m]) -> loss [B]")
+        if loss_fn is not None and stop_rule is not None:
+            raise LfsdError("loss_fn does not combine with stop_rule yet: the dense batch of the seeds still learning would have to "
+                            "hand loss_fn its row ids")
+        self.loss_fn, self.grad_scale = loss_fn, float(grad_scale)
         if interplation_level not in (1, 2):
             raise LfsdError("interplation_level must be 1 (linear) or 2 (cubic), got %r" % (interplation_level,))
         self.interplation_level = interplation_level
@@ -592,10 +670,14 @@ class SparseDemoLearner:
         self.hz = hz.expand(B).contiguous() if hz.dim() == 0 else hz
         tt = oc._t(taus)
         self.taus = tt.unsqueeze(0).expand(B, -1).contiguous() if tt.dim() == 1 else tt
-        wp = oc._t(waypoints)
-        self.wps = wp.unsqueeze(0).expand(B, -1, -1).contiguous() if wp.dim() == 2 else wp
-        self.iface = None if interface_idx is None else torch.as_tensor(list(interface_idx), dtype=torch.int32, device=self.x0.device)
-        oc.check_waypoints(self.taus, self.hz, interface_idx)
+        if loss_fn is not None and waypoints is None:      # (a user-written loss keeps its own targets)
+            self.wps, self.iface = None, None
+            oc.check_time_range(self.taus, self.hz)
+        else:
+            wp = oc._t(waypoints)
+            self.wps = wp.unsqueeze(0).expand(B, -1, -1).contiguous() if wp.dim() == 2 else wp
+            self.iface = None if interface_idx is None else torch.as_tensor(list(interface_idx), dtype=torch.int32, device=self.x0.device)
+            oc.check_waypoints(self.taus, self.hz, interface_idx)
         th = oc._t(theta0)
         th = th.unsqueeze(0) if th.dim() == 1 else th
         if mode == "shared":
@@ -680,6 +762,11 @@ class SparseDemoLearner:
                                            workspace=self._ws, out=self._sol_out())
         self._ws = self._sol["workspace"]
         phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
+        if self.loss_fn is not None:
+            loss, grad = self._evaluate_loss_fn(phase)
+            if self.skip_unconverged:
+                loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
+            return loss, grad
         # a learner that freezes unconverged rows anyway does not pay for differentiating them (they are masked by their
         # status below): the diverged seeds of a fixed learning rate otherwise hold the Riccati launch 20x longer
         self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, Z_grid=self._Z,
@@ -691,6 +778,45 @@ class SparseDemoLearner:
         if self.skip_unconverged:
             loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
         return loss, grad
+
+    def _evaluate_loss_fn(self, phase):
+        """(loss [B], grad [B,p]) of the user-written loss at the solution just computed (class docstring)."""
+        oc, lib, hook = self.oc, self.lib, self.event_hook
+        self._aux = oc.auxSysSolverBatch(self._sol, want_grids=True, Z_grid=self._Z, out=self._aux_out(), phase_hook=phase,
+                                         validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
+                                         interplation_level=self.interplation_level)
+        self._Z = self._aux["Z_grid"]
+        if hook is not None:
+            hook("loss_fn")
+        sol = self._sol
+        if self._aux["curvature"] is not None:      # level 2: the curvature grids the sweeps fitted serve the sampling too
+            sol = dict(sol, curvature=self._aux["curvature"])
+        s = oc.sampleBatch(sol, self.taus, self.interplation_level, validate=False)
+        with torch.enable_grad():
+            x_tau = s["state"].detach().requires_grad_(True)
+            u_tau = s["control"].detach().requires_grad_(True)
+            loss = self.loss_fn(x_tau, u_tau)
+            if not isinstance(loss, torch.Tensor) or tuple(loss.shape) != (self.B,):
+                raise LfsdError("loss_fn must return one loss per trajectory, a [%d] tensor (got %s)"
+                                % (self.B, tuple(loss.shape) if isinstance(loss, torch.Tensor) else type(loss)))
+            rx, ru = torch.autograd.grad(loss.sum(), (x_tau, u_tau), allow_unused=True)
+        aX, aU = self._aux["auxX_grid"], self._aux["auxU_grid"]
+        ad = aX.dtype                               # (the sweeps' arithmetic: aux_dtype may differ from the solve's)
+        cv = lambda t: t.to(ad).contiguous()
+        rx = torch.zeros_like(x_tau) if rx is None else rx
+        grad = lib.waypoint_vjp(cv(self.hz), cv(self.taus), cv(rx), aX, ru=None if ru is None else cv(ru),
+                                auxU_grid=None if ru is None else aU)
+        if self.grad_scale != 1.0:
+            grad = grad * self.grad_scale
+        # a row the sweeps skipped has NaN sensitivity grids and so a NaN gradient; its loss is NaN too, as the fused loss's
+        # (its solve may have left finite state grids behind)
+        status, loss = self._sol.get("status"), loss.detach()
+        if status is not None:
+            skipped = status == 4
+            if self.skip_unconverged:
+                skipped = skipped | (status == 3)
+            loss = torch.where(skipped, torch.full_like(loss, float("nan")), loss)
+        return loss.to(self.theta.dtype), grad.to(self.theta.dtype)
 
     def mask_unconverged(self, status, loss, grad, stats=None):
         """Rows whose OC solve neither converged (1) nor stalled at working precision (2), whose loss / gradient is

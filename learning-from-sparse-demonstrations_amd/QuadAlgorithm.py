@@ -11,7 +11,9 @@ Extension: ``run(..., initial_parameters=[B,7])`` learns B independent seeds in 
 loop when EVERY seed has passed the reference's stop test; ``stop="per_seed"`` gives every seed that test on its own
 (QuadAlgorithm.py:239-257 as the reference runs it, one seed per run): a seed that passes is frozen and leaves the launches, the
 loop ends when none is left; ``results['stop_iter']`` [B] is the number of iterations each seed took (0: still learning at
-``iter_num``), and the traces stay rectangular -- a stopped seed's last entry is repeated.
+``iter_num``), and the traces stay rectangular -- a stopped seed's last entry is repeated.  ``sample_all=True`` adds the final
+trajectories of all seeds, ``results['opt_state_traj_all']`` [B,101,n] and ``results['opt_control_traj_all']`` [B,101,m] (one batched
+solve at every seed's final parameters, sampled on the device: ``COCSys.sampleBatch``); the reference's keys stay those of seed 0.
 """
 import os
 import time
@@ -116,7 +118,7 @@ class QuadAlgorithm(object):
             raise Exception("Wrong optimization method type!")
 
     def run(self, QuadInitialCondition, QuadDesiredStates, SparseInput, ObsList=(), print_flag=False, save_flag=False,
-            initial_parameters=None, save_dir=None, stop="all"):
+            initial_parameters=None, save_dir=None, stop="all", sample_all=False):
         if stop not in ("all", "per_seed"):
             raise ValueError("stop must be 'all' or 'per_seed'")
         t0 = time.time()
@@ -162,6 +164,12 @@ class QuadAlgorithm(object):
                    'time_grid': self.time_list_sparse, 'time_steps': time_steps,
                    'opt_state_traj': opt_traj[:, :n], 'opt_control_traj': opt_traj[:, n:n + m],
                    'horizon': horizon, 'T': self.time_horizon, 'seconds': time.time() - t0}
+        if sample_all:      # the final trajectory of EVERY seed (lib/QuadAlgorithm.py:306-317 per seed): one batched solve + sampling
+            th_all = np.asarray(self.parameter_trace[-1], dtype=np.float64)
+            sol = self.oc.cocSolverBatch(np.tile(self.ini_state, (th_all.shape[0], 1)), horizon, th_all)
+            smp = self.oc.sampleBatch(sol, time_steps)
+            results['opt_state_traj_all'] = smp["state"].double().cpu().numpy()
+            results['opt_control_traj_all'] = smp["control"].double().cpu().numpy()
         if stop == "per_seed":
             results['stop_iter'] = self.learner.stop_iter.cpu().numpy().copy()
         if save_flag:

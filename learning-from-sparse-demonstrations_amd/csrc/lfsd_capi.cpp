@@ -591,3 +591,55 @@ LFSD_API int lfsd_grid_curvature(int dtype, int batch, int n_grid, int n_comp, c
   if (dtype == LFSD_F64) return lfsd_detail::launch_grid_curvature_f64(batch, n_grid, n_comp, (const double*)grid, (double*)curv, stream);
   return LFSD_EINVAL;
 }
+
+// ---- ABI 12: the interpolants at arbitrary times, and the chain rule of a user-written loss (cpdp_sample.h) ----
+// [lo, lo + bytes) and [p, p + other) overlap (a NULL `p` overlaps nothing)
+static bool spans_overlap(const void* lo, unsigned long long bytes, const void* p, unsigned long long other) {
+  if (!p) return false;
+  const unsigned long long a = (unsigned long long)(size_t)lo, b = (unsigned long long)(size_t)p;
+  return a < b + other && b < a + bytes;
+}
+
+LFSD_API int lfsd_sample_grid(int dtype, int batch, int n_grid, int n_comp, int n_times, int times_per_traj, const void* grid,
+                              const void* curv, const void* horizon, const void* times, void* out, void* stream) {
+  if (batch <= 0 || n_grid < 1 || n_comp <= 0 || n_times <= 0 || (times_per_traj != 0 && times_per_traj != 1)) return LFSD_EINVAL;
+  if (curv && n_grid < 3) return LFSD_EINVAL;      // (scipy's cubic needs four nodes)
+  if (!grid || !horizon || !times || !out) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch;
+  const unsigned long long grid_bytes = B * (unsigned long long)(n_grid + 1) * n_comp * es, out_bytes = B * n_times * n_comp * es;
+  if (spans_overlap(out, out_bytes, grid, grid_bytes) || spans_overlap(out, out_bytes, curv, grid_bytes) ||
+      spans_overlap(out, out_bytes, horizon, B * es) || spans_overlap(out, out_bytes, times, (times_per_traj ? B : 1ull) * n_times * es))
+    return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::SampleArgs<float> a{batch, n_grid, n_comp, n_times, times_per_traj, (const float*)grid, (const float*)curv,
+                              (const float*)horizon, (const float*)times, (float*)out};
+    return lfsd_detail::launch_grid_sample_f32(a, stream);
+  }
+  lfsd::SampleArgs<double> a{batch, n_grid, n_comp, n_times, times_per_traj, (const double*)grid, (const double*)curv,
+                             (const double*)horizon, (const double*)times, (double*)out};
+  return lfsd_detail::launch_grid_sample_f64(a, stream);
+}
+
+LFSD_API int lfsd_waypoint_vjp(int dtype, int batch, int n_grid, int n_state, int n_control, int n_param, int n_waypoints,
+                               const void* horizon, const void* taus, const void* rx, const void* ru, const void* auxX_grid,
+                               const void* auxU_grid, void* grad, void* stream) {
+  if (batch <= 0 || n_grid < 1 || n_state <= 0 || n_control <= 0 || n_param <= 0 || n_waypoints <= 0) return LFSD_EINVAL;
+  if (!horizon || !taus || !rx || !auxX_grid || !grad) return LFSD_EINVAL;
+  if ((ru == nullptr) != (auxU_grid == nullptr)) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, K = (unsigned long long)n_waypoints;
+  const unsigned long long nodes = B * (unsigned long long)(n_grid + 1) * n_param, gb = B * n_param * es;
+  if (spans_overlap(grad, gb, horizon, B * es) || spans_overlap(grad, gb, taus, B * K * es) ||
+      spans_overlap(grad, gb, rx, B * K * n_state * es) || spans_overlap(grad, gb, ru, B * K * n_control * es) ||
+      spans_overlap(grad, gb, auxX_grid, nodes * n_state * es) || spans_overlap(grad, gb, auxU_grid, nodes * n_control * es))
+    return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::WaypointVjpArgs<float> a{batch, n_grid, n_state, n_control, n_param, n_waypoints, (const float*)horizon, (const float*)taus,
+                                   (const float*)rx, (const float*)ru, (const float*)auxX_grid, (const float*)auxU_grid, (float*)grad};
+    return lfsd_detail::launch_waypoint_vjp_f32(a, stream);
+  }
+  lfsd::WaypointVjpArgs<double> a{batch, n_grid, n_state, n_control, n_param, n_waypoints, (const double*)horizon, (const double*)taus,
+                                  (const double*)rx, (const double*)ru, (const double*)auxX_grid, (const double*)auxU_grid, (double*)grad};
+  return lfsd_detail::launch_waypoint_vjp_f64(a, stream);
+}

@@ -1,4 +1,5 @@
-// Launchers of interpolation level 2 (ABI 11): the two auxiliary sweeps along the cubic interpolant and the curvature fit.  They live
+// Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
+// the sampling kernels (ABI 12: cpdp_sample.h).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -40,4 +41,24 @@ int launch_grid_curvature_f32(int batch, int n_grid, int n_comp, const float* gr
 int launch_grid_curvature_f64(int batch, int n_grid, int n_comp, const double* grid, double* curv, void* stream) {
   return launch_grid_curvature<double>(batch, n_grid, n_comp, grid, curv, stream);
 }
+// ---- ABI 12: opt_sol(t) / auxsys_sol(t) for a batch, and the chain rule of a user-written loss (cpdp_sample.h) ----
+template <typename T> static int launch_grid_sample(const lfsd::SampleArgs<T>& a, void* stream) {
+  const long long rows = (long long)a.batch * a.n_times;      // (below 2^62; the product with n_comp must not wrap either)
+  if (rows > (0x7fffffffLL * kSplineBlock) / a.n_comp) return LFSD_EINVAL;
+  const long long blocks = (rows * a.n_comp + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::grid_sample_kernel<T>), (unsigned)blocks, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_grid_sample_f32(const lfsd::SampleArgs<float>& a, void* stream) { return launch_grid_sample<float>(a, stream); }
+int launch_grid_sample_f64(const lfsd::SampleArgs<double>& a, void* stream) { return launch_grid_sample<double>(a, stream); }
+template <typename T> static int launch_waypoint_vjp(const lfsd::WaypointVjpArgs<T>& a, void* stream) {
+  const long long threads = (long long)a.batch * a.n_param;
+  const long long blocks = (threads + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::waypoint_vjp_kernel<T>), (unsigned)blocks, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_waypoint_vjp_f32(const lfsd::WaypointVjpArgs<float>& a, void* stream) { return launch_waypoint_vjp<float>(a, stream); }
+int launch_waypoint_vjp_f64(const lfsd::WaypointVjpArgs<double>& a, void* stream) { return launch_waypoint_vjp<double>(a, stream); }
 }

@@ -71,4 +71,9 @@ int launch_forward_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCub
 int launch_forward_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a);
 int launch_grid_curvature_f32(int batch, int n_grid, int n_comp, const float* grid, float* curv, void* stream);
 int launch_grid_curvature_f64(int batch, int n_grid, int n_comp, const double* grid, double* curv, void* stream);
+// sampling the interpolants / chain rule of a user-written loss (ABI 12, cpdp_sample.h; the same third unit)
+int launch_grid_sample_f32(const lfsd::SampleArgs<float>& a, void* stream);
+int launch_grid_sample_f64(const lfsd::SampleArgs<double>& a, void* stream);
+int launch_waypoint_vjp_f32(const lfsd::WaypointVjpArgs<float>& a, void* stream);
+int launch_waypoint_vjp_f64(const lfsd::WaypointVjpArgs<double>& a, void* stream);
 }

@@ -106,7 +106,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
                   "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
@@ -273,7 +273,7 @@ class ModelLibrary:
     EXPORTS = ("lfsd_get_model_info", "lfsd_interface_dim", "lfsd_const_default", "lfsd_coc_workspace_bytes", "lfsd_coc_solve",
                "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
-               "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic")
+               "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -304,6 +304,8 @@ class ModelLibrary:
         L.lfsd_aux_riccati_cubic.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, cd, vp, vp, ci, vp]
         L.lfsd_aux_forward_cubic.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp,
                                              ci, cd, vp, vp, ci, vp]
+        L.lfsd_sample_grid.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.lfsd_waypoint_vjp.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_optimizer_step.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_lookahead.argtypes = [ci, ctypes.c_longlong, cd, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
@@ -311,7 +313,7 @@ class ModelLibrary:
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 11:
+        if rc != 0 or info.abi_version != 12:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -445,6 +447,73 @@ class ModelLibrary:
         with self._on(grid):
             rc = self.lib.lfsd_grid_curvature(_DT[grid.dtype], B, N1 - 1, C, self._p(grid), self._p(out), self._stream(grid))
         self._rc(rc, "lfsd_grid_curvature")
+        return out
+
+    def sample_grid(self, grid, horizon, times, curv=None, out=None):
+        """The batched call of an interpolant (include/lfsd_cpdp.h, ABI 12): ``interp1d(time_grid, grid[b])(times)`` for every
+        trajectory -- linear (CPDP.py:386) or, with ``curv`` (``grid_curvature(grid)``), scipy's cubic (CPDP.py:388-390).
+        grid [B, n_grid+1, C], horizon [B], times [B, K] or [K] (shared by the batch) -> [B, K, C].  Times outside [0, horizon]
+        extrapolate the end interval (the range check is the caller's: COCSys.sampleBatch); a NaN time gives a NaN row."""
+        if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+            raise LfsdError("grid must be a [B, n_grid+1, n_comp] tensor")
+        if grid.dtype not in _DT:
+            raise LfsdError("grid has dtype %s: float32 or float64" % grid.dtype)
+        dt = grid.dtype
+        B, N1, C = grid.shape
+        self._check(grid, (B, N1, C), dt, "grid")
+        self._check(horizon, (B,), dt, "horizon")
+        if not isinstance(times, torch.Tensor) or times.dim() not in (1, 2) or times.shape[-1] < 1:
+            raise LfsdError("times must be a [B, K] or [K] tensor with K >= 1")
+        K = times.shape[-1]
+        self._check(times, (B, K) if times.dim() == 2 else (K,), dt, "times")
+        if N1 < 2 or (curv is not None and N1 < 4):
+            raise LfsdError("n_grid = %d: the linear interpolant needs two nodes, the cubic one four" % (N1 - 1))
+        self._check(curv, (B, N1, C), dt, "curv", optional=True)
+        if out is None:
+            out = torch.empty((B, K, C), dtype=dt, device=grid.device)
+        self._check(out, (B, K, C), dt, "out")
+        with self._on(grid):
+            rc = self.lib.lfsd_sample_grid(_DT[dt], B, N1 - 1, C, K, 1 if times.dim() == 2 else 0, self._p(grid), self._p(curv),
+                                           self._p(horizon), self._p(times), self._p(out), self._stream(grid))
+        self._rc(rc, "lfsd_sample_grid")
+        return out
+
+    def waypoint_vjp(self, horizon, taus, rx, auxX_grid, ru=None, auxU_grid=None, out=None):
+        """grad [B, p] = sum_k rx[:, k] . dx/dtheta(tau_k) (+ ru[:, k] . du/dtheta(tau_k)) on the linear interpolants of the
+        sensitivity grids (include/lfsd_cpdp.h, ABI 12): the chain rule of a user-written loss through ``auxsys_sol``.
+        horizon [B], taus [B, K], rx [B, K, n], auxX_grid [B, n_grid+1, p, n]; ru [B, K, m] and auxU_grid [B, n_grid+1, p, m]
+        together or not at all.  Fixed summation order: a row's gradient is the same bits in any batch."""
+        if not isinstance(auxX_grid, torch.Tensor) or auxX_grid.dim() != 4:
+            raise LfsdError("auxX_grid must be a [B, n_grid+1, n_param, n_state] tensor")
+        if auxX_grid.dtype not in _DT:
+            raise LfsdError("auxX_grid has dtype %s: float32 or float64" % auxX_grid.dtype)
+        dt = auxX_grid.dtype
+        B, N1, p, n = auxX_grid.shape
+        if (ru is None) != (auxU_grid is None):
+            raise LfsdError("ru and auxU_grid go together")
+        if not isinstance(taus, torch.Tensor) or taus.dim() != 2 or taus.shape[1] < 1:
+            raise LfsdError("taus must be a [B, K] tensor with K >= 1")
+        K = taus.shape[1]
+        self._check(auxX_grid, (B, N1, p, n), dt, "auxX_grid")
+        self._check(horizon, (B,), dt, "horizon")
+        self._check(taus, (B, K), dt, "taus")
+        self._check(rx, (B, K, n), dt, "rx")
+        m = self.n_control
+        if ru is not None:
+            if not isinstance(auxU_grid, torch.Tensor) or auxU_grid.dim() != 4:
+                raise LfsdError("auxU_grid must be a [B, n_grid+1, n_param, n_control] tensor")
+            m = auxU_grid.shape[3]
+            self._check(auxU_grid, (B, N1, p, m), dt, "auxU_grid")
+            self._check(ru, (B, K, m), dt, "ru")
+        if N1 < 2:
+            raise LfsdError("n_grid = %d: the interpolant needs two nodes" % (N1 - 1))
+        if out is None:
+            out = torch.empty((B, p), dtype=dt, device=auxX_grid.device)
+        self._check(out, (B, p), dt, "out")
+        with self._on(auxX_grid):
+            rc = self.lib.lfsd_waypoint_vjp(_DT[dt], B, N1 - 1, n, m, p, K, self._p(horizon), self._p(taus), self._p(rx), self._p(ru),
+                                            self._p(auxX_grid), self._p(auxU_grid), self._p(out), self._stream(auxX_grid))
+        self._rc(rc, "lfsd_waypoint_vjp")
         return out
 
     def aux_solve(self, horizon, auxvar, consts, state_grid, control_grid, costate_grid, taus, waypoints, iface_idx,
