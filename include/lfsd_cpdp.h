@@ -25,6 +25,9 @@
  *                         true_opt_sol(taus), lib/QuadAlgorithm.py:306-317 opt_sol(linspace(0, T, 101)) (ABI 12)
  *   lfsd_waypoint_vjp     the `diff_loss += r @ auxsys_sol(tau)` of a user-written loss: Examples/pendulum_timewarping.py:72-86,
  *                         Examples/rocket_groundtruth.py:45-70, lib/QuadAlgorithm.py:616-673 (ABI 12)
+ *   lfsd_optimizer_step_rows / lfsd_lookahead_rows   the same update rules with the rule and its hyper-parameters PER ROW: the runs
+ *                         of test/opt_methods_comparison.py and test/*_learning_rate_comparison.py as one batch (ABI 13)
+ *   lfsd_trace_append     loss_trace / parameter_trace of lib/QuadAlgorithm.py:244-252, kept on the device (ABI 13)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -33,7 +36,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 12
+#define LFSD_ABI_VERSION 13
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -278,6 +281,40 @@ int lfsd_optimizer_step(int dtype, int method, int batch, int n_param, int iter_
 
 /* out = theta + mu * v   (Nesterov look-ahead, [B][n_param]) */
 int lfsd_lookahead(int dtype, long long n, double mu, const void* theta, const void* v, void* out, void* stream);
+
+/* ABI 13 -- hyper-parameter sweeps in one batch.  The reference's comparison scripts (test/opt_methods_comparison.py: five update
+ * rules at five learning rates; test/{vanilla,nesterov,adam,nadam,amsgrad}_learning_rate_comparison.py: one rule at four rates)
+ * run QuadAlgorithm.run once per configuration.  Here every ROW of a batch carries its own rule and hyper-parameters:
+ *   method [B] int32 (LFSD_OPT_*), hyper [B][5] of arithmetic type `dtype`: lr, mu, beta1, beta2, eps of the row.
+ * lfsd_optimizer_step_rows is lfsd_optimizer_step with those read per row, expression for expression: a row's theta / m / v / vhat
+ * come out as the bits lfsd_optimizer_step gives when called with that row's rule and values (its double arguments cast to
+ * `dtype` are the entries of `hyper`).  proj_lo, row_active, iter_idx as there.  A row whose method code is not one of the five is
+ * left untouched, and so is the state its rule does not use (m, v, vhat for Vanilla; v, vhat for Nesterov; vhat for Adam / Nadam).
+ * m, v and vhat are all required: the batch may mix rules.
+ * LFSD_EINVAL: a NULL method / hyper / theta / grad / m / v / vhat, batch or n_param <= 0, iter_idx < 0, an unknown dtype. */
+int lfsd_optimizer_step_rows(int dtype, int batch, int n_param, int iter_idx, const int* method, const void* hyper,
+                             void* theta, const void* grad, void* m, void* v, void* vhat,
+                             const void* proj_lo, const int* row_active, void* stream);
+
+/* The evaluation point of such a batch: out[b] = theta[b] + hyper[b][1] * m[b] for a Nesterov row (lib/QuadAlgorithm.py:478), and
+ * out[b] = theta[b], bit for bit, for every other row -- selected on the method, not multiplied by zero: m of an Adam row is its
+ * first moment and may be Inf or NaN.  theta, m, out [B][n_param]; out must not overlap theta or m.
+ * LFSD_EINVAL: a NULL pointer, batch or n_param <= 0, an unknown dtype, `out` overlapping theta or m. */
+int lfsd_lookahead_rows(int dtype, int batch, int n_param, const int* method, const void* hyper,
+                        const void* theta, const void* m, void* out, void* stream);
+
+/* Traces on the device (the reference appends loss and parameters to host lists every iteration, lib/QuadAlgorithm.py:244-252).
+ * For every row with row_active == NULL or row_active[b] != 0:
+ *   loss_trace  [B][capacity]              [b][iter_idx]       = loss[b]
+ *   gnorm_trace [B][capacity]              [b][iter_idx]       = ||grad[b]||_2   (summed in `dtype`, components ascending, by one
+ *                                                                thread, no atomics: the same bits in any batch)
+ *   theta_trace [B][capacity+1][n_param]   [b][iter_idx+1][:]  = theta[b][:]     (slot 0 is theta_0: the caller's)
+ * Any of the three traces may be NULL, not all.  No other word of the traces is written.  loss [B], grad, theta [B][n_param].
+ * LFSD_EINVAL: a NULL loss / grad / theta, all three traces NULL, batch / n_param / capacity <= 0, iter_idx < 0 or >= capacity,
+ * an unknown dtype. */
+int lfsd_trace_append(int dtype, int batch, int n_param, int iter_idx, int capacity,
+                      const void* loss, const void* grad, const void* theta, const int* row_active,
+                      void* loss_trace, void* gnorm_trace, void* theta_trace, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

@@ -641,12 +641,35 @@ class SparseDemoLearner:
     with ``grad_scale=0.5``.  It combines with both modes, ``warm_start``, ``skip_unconverged`` (a skipped row's grids are NaN, so are
     its loss and gradient, and ``mask_unconverged`` freezes it), ``true_loss_print_flag`` and both interpolation levels.  Together
     with ``stop_rule`` it is refused for now: the dense batch of the seeds still learning would have to hand ``loss_fn`` its row ids.
+
+    Hyper-parameter sweeps in one batch (``independent`` mode).  The reference's comparison scripts run one problem under several
+    update rules or learning rates, one ``QuadAlgorithm.run`` each (test/opt_methods_comparison.py, test/*_learning_rate_comparison.py).
+    Here ``method`` may be a sequence of B strings, ``learning_rate`` / ``mu`` / ``beta_1`` / ``beta_2`` / ``epsilon`` each a scalar or
+    a length-B sequence, array or tensor, and ``true_loss_print_flag`` a bool or B bools (it acts on Nesterov rows only, as ever).
+    With every one of them scalar the learner takes the launches it always took.  ANY sequence selects the rows path: the values
+    are assembled as ``hyper`` [B, 5] in fp64 and cast once to theta's dtype -- the numbers ``lfsd_optimizer_step`` gets by casting
+    its double arguments; the evaluation point comes from ``lfsd_lookahead_rows`` (skipped when no row is Nesterov) and the update is
+    ``lfsd_optimizer_step_rows``.  A row walks, bit for bit, the path it walks in a uniform learner with its configuration.  If any
+    Nesterov row has the true-loss flag, the (active) batch is evaluated a second time at theta -- the WHOLE batch, a second solve
+    and two more sweeps -- and only the flagged rows take their loss and gradient from it; every other row is left as its uniform
+    learner, which has no second evaluation, leaves it: the controls and status its next solve starts from (``warm_start`` /
+    ``skip_unconverged``) and its entry of the frozen-row mask the stop test reads stay the first evaluation's.  The arrays stay [B], indexed by original
+    row, through ``stop_rule``; the rows path also combines with ``loss_fn``, ``interplation_level``, ``warm_start`` and
+    ``skip_unconverged``.  A wrong length or ``mode='shared'`` with a per-row argument (there is one theta) raises ``LfsdError``.
+
+    ``trace`` (default ``None``; both modes): ``trace=capacity`` keeps the traces the reference's loop appends to host lists
+    (lib/QuadAlgorithm.py:244-252) on the device: ``loss_trace`` and ``grad_norm_trace`` [B, capacity], ``theta_trace``
+    [B, capacity+1, p], filled with NaN, ``theta_trace[:, 0]`` = theta_0.  One ``lfsd_trace_append`` per step files what ``step()``
+    returns and theta after the projection; nothing is read back.  With a stop rule the launch gets the seeds active as of the
+    previous test: a seed is traced in the step in which it stops and never after -- its later entries stay NaN, as the reference's
+    trace simply ends there (a row ``skip_unconverged`` froze for one step is traced: it repeats its theta).  A step beyond the
+    capacity raises ``LfsdError``.  In ``shared`` mode the traces have the single row.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
-                 skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0):
+                 skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
         if loss_fn is not None and not callable(loss_fn):
             raise LfsdError("loss_fn must be callable: loss_fn(x_tau [B,K,n], u_tau [B,K,m]) -> loss [B]")
@@ -658,8 +681,9 @@ class SparseDemoLearner:
             raise LfsdError("interplation_level must be 1 (linear) or 2 (cubic), got %r" % (interplation_level,))
         self.interplation_level = interplation_level
         self.b1, self.b2, self.eps = beta_1, beta_2, epsilon
-        if method not in runtime.OPT_METHODS:
-            raise Exception("Wrong optimization method type!")
+        for mth in (list(method) if isinstance(method, (list, tuple, np.ndarray)) else [method]):
+            if not isinstance(mth, str) or mth not in runtime.OPT_METHODS:
+                raise Exception("Wrong optimization method type!")
         self.mode, self.pg = mode, process_group
         self.lib = oc.compile()
         x0 = oc._t(ini_state)
@@ -694,6 +718,8 @@ class SparseDemoLearner:
         self.proj_lo = lo.to(device=self.x0.device, dtype=self.theta.dtype)
         self.iter_idx = 0
         self.true_loss = true_loss_print_flag
+        self._init_rows(method, learning_rate, mu, beta_1, beta_2, epsilon, true_loss_print_flag)
+        self._init_trace(trace)
         # warm_start: start every OC solve from the previous iteration's controls (theta moves little per step).
         # The reference cold-starts IPOPT every time; the converged KKT point is the same, only the path to it is shorter.
         self.warm_start = warm_start
@@ -728,6 +754,111 @@ class SparseDemoLearner:
             self._prev = None            # (controls, status) of the previous solve of the rows now active, dense
             self._loss_full = self._grad_full = None
         self.n_active = B
+
+    # ---- per-row update rules (hyper-parameter sweeps in one batch) and device traces -------------------------------------
+    @staticmethod
+    def _per_row(x):
+        """None for a scalar argument, else its values as a list."""
+        if isinstance(x, torch.Tensor):
+            return None if x.dim() == 0 else x.detach().cpu().tolist()
+        if isinstance(x, np.ndarray):
+            return None if x.ndim == 0 else x.tolist()
+        if isinstance(x, (list, tuple)):
+            return list(x)
+        return None
+
+    def _init_rows(self, method, learning_rate, mu, beta_1, beta_2, epsilon, true_loss):
+        B, dev = self.B, self.x0.device
+        seqs = dict(method=list(method) if isinstance(method, (list, tuple, np.ndarray)) else None, learning_rate=self._per_row(learning_rate),
+                    mu=self._per_row(mu), beta_1=self._per_row(beta_1), beta_2=self._per_row(beta_2), epsilon=self._per_row(epsilon),
+                    true_loss_print_flag=self._per_row(true_loss))
+        self._rows_path = any(v is not None for v in seqs.values())
+        if not self._rows_path:
+            return
+        if self.mode == "shared":
+            raise LfsdError("per-row %s: mode='shared' keeps one theta for all demonstrations (mode='independent' only)"
+                            % ", ".join(k for k, v in seqs.items() if v is not None))
+        for k, v in seqs.items():
+            if v is not None and len(v) != B:
+                raise LfsdError("%s has %d entries for a batch of %d rows" % (k, len(v), B))
+        full = lambda v, scalar: [scalar] * B if v is None else v
+        methods = full(seqs["method"], method)
+        codes = np.array([runtime.OPT_METHODS[mth] for mth in methods], dtype=np.int32)
+        # assembled in fp64, cast once: the numbers lfsd_optimizer_step gets by casting its double arguments
+        hyper = np.stack([np.asarray(full(seqs[k], sc), dtype=np.float64) for k, sc in
+                          (("learning_rate", learning_rate), ("mu", mu), ("beta_1", beta_1), ("beta_2", beta_2),
+                           ("epsilon", epsilon))], axis=1)
+        self.method = list(methods)
+        self._method_rows = torch.from_numpy(codes).to(dev)
+        self._hyper = torch.from_numpy(hyper).to(device=dev, dtype=self.theta.dtype).contiguous()
+        nesterov = codes == runtime.OPT_METHODS["Nesterov"]
+        self._any_nesterov = bool(nesterov.any())
+        flagged = nesterov & np.array([bool(f) for f in full(seqs["true_loss_print_flag"], true_loss)])
+        self._true_rows = torch.from_numpy(flagged).to(dev) if flagged.any() else None
+
+    def _init_trace(self, trace):
+        self.loss_trace = self.grad_norm_trace = self.theta_trace = None
+        self._trace_cap = None
+        if trace is None:
+            return
+        if isinstance(trace, bool) or int(trace) != trace or int(trace) <= 0:
+            raise LfsdError("trace is None or the capacity of the traces, a positive number of steps (got %r)" % (trace,))
+        cap, th = int(trace), self.theta
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=th.dtype, device=th.device)
+        self._trace_cap = cap
+        self.loss_trace, self.grad_norm_trace = nan(th.shape[0], cap), nan(th.shape[0], cap)
+        self.theta_trace = nan(th.shape[0], cap + 1, th.shape[1])
+        self.theta_trace[:, 0] = th
+
+    def _check_trace_room(self):
+        if self._trace_cap is not None and self.iter_idx >= self._trace_cap:
+            raise LfsdError("step %d does not fit the traces: trace=%d" % (self.iter_idx + 1, self._trace_cap))
+
+    def _eval_point(self):
+        """Where the update rules want loss and gradient: theta, or the Nesterov look-ahead point (QuadAlgorithm.py:478)."""
+        if not self._rows_path:
+            return self.lib.lookahead(self.theta, self.m, self.mu) if self.method == "Nesterov" else self.theta
+        if not self._any_nesterov:
+            return self.theta
+        return self.lib.lookahead_rows(self._method_rows, self._hyper, self.theta, self.m)
+
+    def _update(self, grad, row_active):
+        if not self._rows_path:
+            self.lib.optimizer_step(self.method, self.theta, grad, self.iter_idx, self.lr, self.mu, self.b1, self.b2, self.eps,
+                                    m=self.m, v=self.v, vhat=self.vhat, proj_lo=self.proj_lo, row_active=row_active)
+        else:
+            self.lib.optimizer_step_rows(self._method_rows, self._hyper, self.theta, grad, self.iter_idx, self.m, self.v, self.vhat,
+                                         proj_lo=self.proj_lo, row_active=row_active)
+
+    def _start_state(self):
+        """(controls, status) the next solve of the rows now evaluated starts from (warm_start / skip_unconverged), or None."""
+        if not (self.warm_start or self.skip_unconverged):
+            return None
+        if self._stop is not None and self.n_active < self.B:
+            return self._prev
+        return None if self._sol is None else (self._sol["control_grid"], self._sol["status"])
+
+    def _second_evaluation(self, evaluate, flag):
+        """The evaluation at theta that flagged Nesterov rows take their loss and gradient from (QuadAlgorithm.py:487-492), run on
+        the whole (active) batch.  Every OTHER row is left as its uniform learner leaves it, which has no second evaluation: the
+        controls and status its next solve starts from, and its entry of the frozen-row mask, stay those of the first evaluation.
+        `flag` [rows evaluated] bool.  Returns what `evaluate()` returns."""
+        first, ok1 = self._start_state(), self._ok
+        if first is not None:
+            first = tuple(t.clone() for t in first)
+        out = evaluate()
+        if first is not None:
+            for t, t1 in zip(self._start_state(), first):
+                t.copy_(torch.where(flag.reshape((-1,) + (1,) * (t.dim() - 1)), t, t1))
+        if ok1 is not None and self._ok is not None:
+            self._ok = torch.where(flag, self._ok, ok1)
+        return out
+
+    def _append_trace(self, loss, grad, row_active):
+        """After the update of iteration iter_idx - 1: what step() returns and theta after the projection."""
+        if self._trace_cap is not None:
+            self.lib.trace_append(self.iter_idx - 1, loss.contiguous(), grad.contiguous(), self.theta, loss_trace=self.loss_trace,
+                                  gnorm_trace=self.grad_norm_trace, theta_trace=self.theta_trace, row_active=row_active)
 
     @property
     def active(self):
@@ -935,10 +1066,9 @@ class SparseDemoLearner:
         evaluation point, solve / differentiate n_active rows, scatter loss / gradient, masked update, test."""
         if self.n_active == 0:
             return self._loss_full, self._grad_full
+        self._check_trace_room()
         lib, B, n = self.lib, self.B, self.n_active
-        theta_eval = self.theta
-        if self.method == "Nesterov":
-            theta_eval = lib.lookahead(self.theta, self.m, self.mu)      # QuadAlgorithm.py:478
+        theta_eval = self._eval_point()
         loss, grad, loss_full, grad_full = self._evaluate_stop_rule(theta_eval)
         hook = self.event_hook
         if hook is not None:
@@ -949,13 +1079,24 @@ class SparseDemoLearner:
             row_active = ok if n == B else lib.scatter_rows(self._rows[self._cur], ok, self._active.clone(), n)
             if self.count_unconverged:
                 self.n_unconverged = int(n - self._ok.sum().item())
-        lib.optimizer_step(self.method, self.theta, grad_full, self.iter_idx, self.lr, self.mu, self.b1, self.b2, self.eps,
-                           m=self.m, v=self.v, vhat=self.vhat, proj_lo=self.proj_lo, row_active=row_active)
+        self._update(grad_full, row_active)
         self.iter_idx += 1
         if hook is not None:
             hook("end")
-        if self.method == "Nesterov" and self.true_loss:      # QuadAlgorithm.py:487-492: the loss the reference's loop then tests
+        if self._rows_path:
+            if self._true_rows is not None:      # flagged Nesterov rows only take the second evaluation (of the whole active batch)
+                loss, grad = loss.clone(), grad.clone()      # (the solver's buffers: the second evaluation writes them again)
+                flag = self._true_rows if n == B else self._true_rows[self._rows[self._cur][:n].long()]
+                l2, g2, _, _ = self._second_evaluation(lambda: self._evaluate_stop_rule(self.theta), flag)
+                loss, grad = torch.where(flag, l2, loss), torch.where(flag.unsqueeze(1), g2, grad)
+                loss_full, grad_full = loss, grad
+                if n < B:
+                    rows = self._rows[self._cur]
+                    loss_full = lib.scatter_rows(rows, loss, self._loss_full, n)
+                    grad_full = lib.scatter_rows(rows, grad, self._grad_full, n)
+        elif self.method == "Nesterov" and self.true_loss:      # QuadAlgorithm.py:487-492: the loss the reference's loop then tests
             loss, grad, loss_full, grad_full = self._evaluate_stop_rule(self.theta)
+        self._append_trace(loss_full, grad_full, None if n == B else self._active)      # (active as of the previous test)
         self._apply_stop_rule(loss, grad)
         if self._loss_full is not None:
             return self._loss_full, self._grad_full
@@ -965,9 +1106,8 @@ class SparseDemoLearner:
         """One outer iteration; returns (loss, grad) evaluated where the update rule needs them."""
         if self._stop is not None:
             return self._step_stop_rule()
-        theta_eval = self.theta
-        if self.method == "Nesterov":
-            theta_eval = self.lib.lookahead(self.theta, self.m, self.mu)      # QuadAlgorithm.py:478
+        self._check_trace_room()
+        theta_eval = self._eval_point()
         self._ok = None
         loss, grad = self.evaluate(theta_eval)
         hook = self.event_hook
@@ -992,14 +1132,19 @@ class SparseDemoLearner:
                 row_active = self._ok.to(torch.int32)
                 if self.count_unconverged:
                     self.n_unconverged = int(self.B - self._ok.sum().item())
-        self.lib.optimizer_step(self.method, self.theta, grad_used, self.iter_idx, self.lr, self.mu, self.b1,
-                                self.b2, self.eps, m=self.m, v=self.v, vhat=self.vhat, proj_lo=self.proj_lo,
-                                row_active=row_active)
+        self._update(grad_used, row_active)
         self.iter_idx += 1
         if hook is not None:
             hook("end")
-        if self.method == "Nesterov" and self.true_loss:
+        if self._rows_path:
+            if self._true_rows is not None:      # flagged Nesterov rows only take the second evaluation (of the whole batch)
+                loss_out, grad_used = loss_out.clone(), grad_used.clone()      # (the solver's buffers: written again below)
+                l2, g2 = self._second_evaluation(lambda: self.evaluate(self.theta), self._true_rows)
+                loss_out = torch.where(self._true_rows, l2, loss_out)
+                grad_used = torch.where(self._true_rows.unsqueeze(1), g2, grad_used)
+        elif self.method == "Nesterov" and self.true_loss:
             loss_out, grad_used = self.evaluate(self.theta)                   # QuadAlgorithm.py:487-492
             if self.mode == "shared":
                 loss_out, grad_used = loss_out.sum().reshape(1), grad_used.sum(dim=0, keepdim=True)
+        self._append_trace(loss_out, grad_used, None)
         return loss_out, grad_used

@@ -7,6 +7,9 @@ Plotting / animation (QuadAlgorithm.py:260-281, 354-451, 581-613) is UI and is n
 dictionary the reference saves to ``data/uav_results_random_*.mat`` (QuadAlgorithm.py:324-333) and writes it only if
 ``save_flag`` is set.
 
+``run_comparison(para_list, ...)`` is the batched form of the reference's test/*_comparison.py scripts: every configuration a block
+of rows of one learner, traces kept on the device.
+
 Extension: ``run(..., initial_parameters=[B,7])`` learns B independent seeds in lock-step.  ``stop="all"`` (default) leaves the
 loop when EVERY seed has passed the reference's stop test; ``stop="per_seed"`` gives every seed that test on its own
 (QuadAlgorithm.py:239-257 as the reference runs it, one seed per run): a seed that passes is frozen and leaves the launches, the
@@ -179,6 +182,71 @@ class QuadAlgorithm(object):
             sio.savemat(os.path.join(d, 'uav_results_random_' + time.strftime("%Y%m%d%H%M%S") + '.mat'),
                         {'results': results})
         return results
+
+    def run_comparison(self, para_list, QuadInitialCondition, QuadDesiredStates, SparseInput, initial_parameters=None):
+        """The comparison scripts of the reference (test/opt_methods_comparison.py, test/*_learning_rate_comparison.py: one
+        ``load_optimization_function`` + ``run`` per configuration, the loss traces overlaid) as ONE batch.  ``para_list``: the
+        dictionaries ``load_optimization_function`` takes, with equal ``iter_num`` (else ``ValueError``); ``initial_parameters``: one
+        theta_0 [7] (default: the reference's) or S seeds [S, 7], given to every configuration.  One learner of
+        ``len(para_list) x S`` rows (configuration-major), every row with its own update rule, hyper-parameters and the reference's
+        stop test (``stop_rule=dict(loss=0.9, grad_norm=0.05)``: each of the reference's runs has its own), traces on the device
+        (``trace=iter_num``); the loop reads one int per step, the number of rows still learning.  Returns a dictionary:
+          ``loss_trace_comparison``  per configuration what ``run(..., stop="per_seed")`` leaves in ``loss_trace`` for it: [stop_iter]
+                                     for one theta_0, [iters, S] for seeds (iters: the configuration's slowest seed; a stopped seed's
+                                     last entry is repeated, as ``run`` does);
+          ``label_list``             the method names when the methods differ, else ``str(learning_rate)`` -- the scripts' labels;
+          ``parameter_trace``        per configuration [stop_iter + 1, 7] or [iters + 1, S, 7];
+          ``stop_iter``              per configuration the iterations it took, an int or [S] (0: still learning at ``iter_num``).
+        Plotting stays with the caller (``plot_opt_method_comparison`` is UI)."""
+        para_list = list(para_list)
+        if not para_list:
+            raise ValueError("run_comparison needs at least one configuration")
+        if len({int(para["iter_num"]) for para in para_list}) != 1:
+            raise ValueError("the configurations of one comparison share iter_num (got %s)" % [para["iter_num"] for para in para_list])
+        C = len(para_list)
+        rows = dict(method=[], learning_rate=[], mu=[], beta_1=[], beta_2=[], epsilon=[], true_loss_print_flag=[])
+        for para in para_list:
+            self.load_optimization_function(para)                 # (validates the dictionary as the reference does)
+            kw = dict(dict(mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, true_loss_print_flag=False), **self.opt_kwargs)
+            for k in rows:
+                rows[k].append(dict(kw, method=self.optimization_method_str, learning_rate=self.learning_rate)[k])
+        self.settings(QuadDesiredStates)
+        self.ini_state = (list(QuadInitialCondition.position) + list(QuadInitialCondition.velocity) +
+                          list(QuadInitialCondition.attitude_quaternion) + list(QuadInitialCondition.angular_velocity))
+        self.time_horizon = 1.0                                    # QuadAlgorithm.py:221-223
+        self.time_list_sparse = np.array(SparseInput.time_list) / SparseInput.time_horizon
+        self.waypoints = np.array(SparseInput.waypoints)
+        theta0 = np.array([1, 0.1, 0.1, 0.1, 0.1, 0.1, -1], dtype=float) if initial_parameters is None else \
+            np.asarray(initial_parameters, dtype=float)
+        single = theta0.ndim == 1
+        seeds = theta0.reshape(-1, theta0.shape[-1])
+        S, K = seeds.shape[0], self.iter_num
+        per_row = {k: [v for v in vals for _ in range(S)] for k, vals in rows.items()}
+        self.learner = CPDP.SparseDemoLearner(self.oc, np.tile(self.ini_state, (C * S, 1)), self.time_horizon, self.time_list_sparse,
+                                              self.waypoints, self.interface_pos_idx, np.tile(seeds, (C, 1)),
+                                              stop_rule=dict(loss=0.9, grad_norm=0.05), trace=K, **per_row)
+        for _ in range(K):
+            if self.learner.n_active == 0:
+                break
+            self.learner.step()
+        stop = self.learner.stop_iter.cpu().numpy().reshape(C, S)
+        loss = self.learner.loss_trace.cpu().numpy().reshape(C, S, K)
+        theta = self.learner.theta_trace.cpu().numpy().reshape(C, S, K + 1, -1)
+        took = np.where(stop == 0, K, stop)                        # entries a row's traces hold
+        loss_cmp, par_cmp = [], []
+        for i in range(C):
+            n = int(took[i].max())
+            l, th = loss[i, :, :n].copy(), theta[i, :, :n + 1].copy()
+            for s_ in range(S):                                    # rectangular, as run(): a stopped seed's last entry repeated
+                l[s_, took[i, s_]:] = l[s_, took[i, s_] - 1]
+                th[s_, took[i, s_] + 1:] = th[s_, took[i, s_]]
+            loss_cmp.append(l[0] if single else l.T.copy())
+            par_cmp.append(th[0] if single else th.transpose(1, 0, 2).copy())
+        methods = rows["method"]
+        labels = list(methods) if len(set(methods)) > 1 else [str(lr) for lr in rows["learning_rate"]]
+        self.loss_trace_comparison, self.label_list = loss_cmp, labels
+        return {'loss_trace_comparison': loss_cmp, 'label_list': labels, 'parameter_trace': par_cmp,
+                'stop_iter': [int(stop[i, 0]) if single else stop[i].copy() for i in range(C)]}
 
     def getloss_pos_corrections(self, time_grid, target_waypoints, opt_sol, auxsys_sol):
         """QuadAlgorithm.py:616-639 on host objects returned by cocSolver / auxSysSolver (same formula the kernel fuses)."""

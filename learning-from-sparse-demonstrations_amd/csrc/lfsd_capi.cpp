@@ -643,3 +643,56 @@ LFSD_API int lfsd_waypoint_vjp(int dtype, int batch, int n_grid, int n_state, in
                                   (const double*)rx, (const double*)ru, (const double*)auxX_grid, (const double*)auxU_grid, (double*)grad};
   return lfsd_detail::launch_waypoint_vjp_f64(a, stream);
 }
+
+// ---- ABI 13: hyper-parameter sweeps in one batch -- every row its own update rule and hyper-parameters, traces on the device
+// (cpdp_opt.h; test/opt_methods_comparison.py, test/*_learning_rate_comparison.py, lib/QuadAlgorithm.py:244-252) ----
+LFSD_API int lfsd_optimizer_step_rows(int dtype, int batch, int n_param, int iter_idx, const int* method, const void* hyper,
+                                      void* theta, const void* grad, void* m, void* v, void* vhat, const void* proj_lo,
+                                      const int* row_active, void* stream) {
+  if (batch <= 0 || n_param <= 0 || iter_idx < 0) return LFSD_EINVAL;
+  if (!method || !hyper || !theta || !grad || !m || !v || !vhat) return LFSD_EINVAL;      // (the batch may mix rules: all state)
+  if (dtype == LFSD_F32) {
+    lfsd::OptRowsArgs<float> a{batch, n_param, iter_idx, method, (const float*)hyper, (float*)theta, (const float*)grad, (float*)m,
+                               (float*)v, (float*)vhat, (const float*)proj_lo, row_active};
+    return lfsd_detail::launch_optimizer_rows_f32(a, stream);
+  }
+  if (dtype == LFSD_F64) {
+    lfsd::OptRowsArgs<double> a{batch, n_param, iter_idx, method, (const double*)hyper, (double*)theta, (const double*)grad,
+                                (double*)m, (double*)v, (double*)vhat, (const double*)proj_lo, row_active};
+    return lfsd_detail::launch_optimizer_rows_f64(a, stream);
+  }
+  return LFSD_EINVAL;
+}
+
+LFSD_API int lfsd_lookahead_rows(int dtype, int batch, int n_param, const int* method, const void* hyper, const void* theta,
+                                 const void* m, void* out, void* stream) {
+  if (batch <= 0 || n_param <= 0 || !method || !hyper || !theta || !m || !out) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  const unsigned long long bytes = (unsigned long long)batch * n_param * (dtype == LFSD_F32 ? 4 : 8);
+  if (spans_overlap(out, bytes, theta, bytes) || spans_overlap(out, bytes, m, bytes)) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::LookaheadRowsArgs<float> a{batch, n_param, method, (const float*)hyper, (const float*)theta, (const float*)m, (float*)out};
+    return lfsd_detail::launch_lookahead_rows_f32(a, stream);
+  }
+  lfsd::LookaheadRowsArgs<double> a{batch, n_param, method, (const double*)hyper, (const double*)theta, (const double*)m, (double*)out};
+  return lfsd_detail::launch_lookahead_rows_f64(a, stream);
+}
+
+LFSD_API int lfsd_trace_append(int dtype, int batch, int n_param, int iter_idx, int capacity, const void* loss, const void* grad,
+                               const void* theta, const int* row_active, void* loss_trace, void* gnorm_trace, void* theta_trace,
+                               void* stream) {
+  if (batch <= 0 || n_param <= 0 || capacity <= 0 || iter_idx < 0 || iter_idx >= capacity) return LFSD_EINVAL;
+  if (!loss || !grad || !theta) return LFSD_EINVAL;
+  if (!loss_trace && !gnorm_trace && !theta_trace) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::TraceArgs<float> a{batch, n_param, iter_idx, capacity, (const float*)loss, (const float*)grad, (const float*)theta,
+                             row_active, (float*)loss_trace, (float*)gnorm_trace, (float*)theta_trace};
+    return lfsd_detail::launch_trace_append_f32(a, stream);
+  }
+  if (dtype == LFSD_F64) {
+    lfsd::TraceArgs<double> a{batch, n_param, iter_idx, capacity, (const double*)loss, (const double*)grad, (const double*)theta,
+                              row_active, (double*)loss_trace, (double*)gnorm_trace, (double*)theta_trace};
+    return lfsd_detail::launch_trace_append_f64(a, stream);
+  }
+  return LFSD_EINVAL;
+}

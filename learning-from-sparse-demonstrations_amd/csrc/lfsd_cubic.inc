@@ -61,4 +61,36 @@ template <typename T> static int launch_waypoint_vjp(const lfsd::WaypointVjpArgs
 }
 int launch_waypoint_vjp_f32(const lfsd::WaypointVjpArgs<float>& a, void* stream) { return launch_waypoint_vjp<float>(a, stream); }
 int launch_waypoint_vjp_f64(const lfsd::WaypointVjpArgs<double>& a, void* stream) { return launch_waypoint_vjp<double>(a, stream); }
+// ---- ABI 13: per-row update rules, the evaluation point of a mixed batch, device traces (cpdp_opt.h) ----
+// one thread per (row, parameter); batch and n_param are positive ints, so the thread count stays below 2^62
+static bool rows_grid(int batch, int n_param, unsigned* grid) {
+  const long long blocks = ((long long)batch * n_param + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return false;
+  *grid = (unsigned)blocks;
+  return true;
+}
+template <typename T> static int launch_optimizer_rows(const lfsd::OptRowsArgs<T>& a, void* stream) {
+  unsigned grid;
+  if (!rows_grid(a.batch, a.n_param, &grid)) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::optimizer_rows_kernel<T>), grid, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_optimizer_rows_f32(const lfsd::OptRowsArgs<float>& a, void* stream) { return launch_optimizer_rows<float>(a, stream); }
+int launch_optimizer_rows_f64(const lfsd::OptRowsArgs<double>& a, void* stream) { return launch_optimizer_rows<double>(a, stream); }
+template <typename T> static int launch_lookahead_rows(const lfsd::LookaheadRowsArgs<T>& a, void* stream) {
+  unsigned grid;
+  if (!rows_grid(a.batch, a.n_param, &grid)) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::lookahead_rows_kernel<T>), grid, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_lookahead_rows_f32(const lfsd::LookaheadRowsArgs<float>& a, void* stream) { return launch_lookahead_rows<float>(a, stream); }
+int launch_lookahead_rows_f64(const lfsd::LookaheadRowsArgs<double>& a, void* stream) { return launch_lookahead_rows<double>(a, stream); }
+template <typename T> static int launch_trace_append(const lfsd::TraceArgs<T>& a, void* stream) {
+  unsigned grid;
+  if (!rows_grid(a.batch, a.n_param, &grid)) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::trace_append_kernel<T>), grid, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_trace_append_f32(const lfsd::TraceArgs<float>& a, void* stream) { return launch_trace_append<float>(a, stream); }
+int launch_trace_append_f64(const lfsd::TraceArgs<double>& a, void* stream) { return launch_trace_append<double>(a, stream); }
 }

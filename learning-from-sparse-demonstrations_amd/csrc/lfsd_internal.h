@@ -76,4 +76,11 @@ int launch_grid_sample_f32(const lfsd::SampleArgs<float>& a, void* stream);
 int launch_grid_sample_f64(const lfsd::SampleArgs<double>& a, void* stream);
 int launch_waypoint_vjp_f32(const lfsd::WaypointVjpArgs<float>& a, void* stream);
 int launch_waypoint_vjp_f64(const lfsd::WaypointVjpArgs<double>& a, void* stream);
+// per-row update rules and device traces (ABI 13, cpdp_opt.h; the same third unit)
+int launch_optimizer_rows_f32(const lfsd::OptRowsArgs<float>& a, void* stream);
+int launch_optimizer_rows_f64(const lfsd::OptRowsArgs<double>& a, void* stream);
+int launch_lookahead_rows_f32(const lfsd::LookaheadRowsArgs<float>& a, void* stream);
+int launch_lookahead_rows_f64(const lfsd::LookaheadRowsArgs<double>& a, void* stream);
+int launch_trace_append_f32(const lfsd::TraceArgs<float>& a, void* stream);
+int launch_trace_append_f64(const lfsd::TraceArgs<double>& a, void* stream);
 }

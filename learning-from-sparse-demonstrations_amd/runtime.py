@@ -273,7 +273,8 @@ class ModelLibrary:
     EXPORTS = ("lfsd_get_model_info", "lfsd_interface_dim", "lfsd_const_default", "lfsd_coc_workspace_bytes", "lfsd_coc_solve",
                "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
-               "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp")
+               "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
+               "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -308,12 +309,15 @@ class ModelLibrary:
         L.lfsd_waypoint_vjp.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_optimizer_step.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_lookahead.argtypes = [ci, ctypes.c_longlong, cd, vp, vp, vp, vp]
+        L.lfsd_optimizer_step_rows.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.lfsd_lookahead_rows.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.lfsd_trace_append.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 12:
+        if rc != 0 or info.abi_version != 13:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -640,6 +644,78 @@ class ModelLibrary:
                                          self._p(out), self._stream(theta))
         self._rc(rc, "lfsd_lookahead")
         return out
+
+    # ---- ABI 13: per-row update rules and device traces -------------------------------------------------------------------
+    def _rows_args(self, method, hyper, theta):
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.dtype not in _DT:
+            raise LfsdError("theta must be a [B, n_param] float32 / float64 tensor")
+        B, p = theta.shape
+        self._check(theta, (B, p), theta.dtype, "theta")
+        self._check(method, (B,), torch.int32, "method")
+        self._check(hyper, (B, 5), theta.dtype, "hyper")
+        return B, p, theta.dtype
+
+    def optimizer_step_rows(self, method, hyper, theta, grad, iter_idx, m, v, vhat, proj_lo=None, row_active=None):
+        """``optimizer_step`` with the rule and the hyper-parameters per row (include/lfsd_cpdp.h, ABI 13): method [B] int32
+        (runtime.OPT_METHODS codes), hyper [B, 5] = lr, mu, beta1, beta2, eps in theta's dtype.  Bit for bit what ``optimizer_step``
+        gives each row with its own values; m, v, vhat are all required (the batch may mix rules)."""
+        B, p, dt = self._rows_args(method, hyper, theta)
+        for nm, t in (("grad", grad), ("m", m), ("v", v), ("vhat", vhat)):
+            self._check(t, (B, p), dt, nm)
+        self._check(proj_lo, (p,), dt, "proj_lo", optional=True)
+        self._check(row_active, (B,), torch.int32, "row_active", optional=True)
+        with self._on(theta):
+            rc = self.lib.lfsd_optimizer_step_rows(_DT[dt], B, p, int(iter_idx), self._p(method), self._p(hyper), self._p(theta),
+                                                   self._p(grad), self._p(m), self._p(v), self._p(vhat), self._p(proj_lo),
+                                                   self._p(row_active), self._stream(theta))
+        self._rc(rc, "lfsd_optimizer_step_rows")
+
+    def lookahead_rows(self, method, hyper, theta, m, out=None):
+        """The evaluation point of a mixed batch: theta + mu_b * m for Nesterov rows, a bit copy of theta for every other row."""
+        B, p, dt = self._rows_args(method, hyper, theta)
+        self._check(m, (B, p), dt, "m")
+        if out is None:
+            out = torch.empty_like(theta)
+        self._check(out, (B, p), dt, "out")
+        with self._on(theta):
+            rc = self.lib.lfsd_lookahead_rows(_DT[dt], B, p, self._p(method), self._p(hyper), self._p(theta), self._p(m),
+                                              self._p(out), self._stream(theta))
+        self._rc(rc, "lfsd_lookahead_rows")
+        return out
+
+    def trace_append(self, iter_idx, loss, grad, theta, loss_trace=None, gnorm_trace=None, theta_trace=None, row_active=None):
+        """File loss[b], ||grad[b]||_2 and theta[b] of every active row under iteration ``iter_idx`` (include/lfsd_cpdp.h, ABI 13):
+        loss_trace / gnorm_trace [B, capacity] at [:, iter_idx], theta_trace [B, capacity+1, p] at [:, iter_idx+1].  Any of the
+        three may be None, not all.  Nothing is read back."""
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.dtype not in _DT:
+            raise LfsdError("theta must be a [B, n_param] float32 / float64 tensor")
+        B, p = theta.shape
+        dt = theta.dtype
+        self._check(theta, (B, p), dt, "theta")
+        self._check(grad, (B, p), dt, "grad")
+        self._check(loss, (B,), dt, "loss")
+        given = [t for t in (loss_trace, gnorm_trace) if t is not None]
+        if theta_trace is not None:
+            if not isinstance(theta_trace, torch.Tensor) or theta_trace.dim() != 3:
+                raise LfsdError("theta_trace must be a [B, capacity+1, n_param] tensor")
+            cap = theta_trace.shape[1] - 1
+        elif given:
+            if not isinstance(given[0], torch.Tensor) or given[0].dim() != 2:
+                raise LfsdError("loss_trace / gnorm_trace must be [B, capacity] tensors")
+            cap = given[0].shape[1]
+        else:
+            raise LfsdError("trace_append needs at least one of loss_trace, gnorm_trace, theta_trace")
+        self._check(loss_trace, (B, cap), dt, "loss_trace", optional=True)
+        self._check(gnorm_trace, (B, cap), dt, "gnorm_trace", optional=True)
+        self._check(theta_trace, (B, cap + 1, p), dt, "theta_trace", optional=True)
+        self._check(row_active, (B,), torch.int32, "row_active", optional=True)
+        if not 0 <= int(iter_idx) < cap:
+            raise LfsdError("iteration %d does not fit a trace of capacity %d" % (int(iter_idx), cap))
+        with self._on(theta):
+            rc = self.lib.lfsd_trace_append(_DT[dt], B, p, int(iter_idx), cap, self._p(loss), self._p(grad), self._p(theta),
+                                            self._p(row_active), self._p(loss_trace), self._p(gnorm_trace), self._p(theta_trace),
+                                            self._stream(theta))
+        self._rc(rc, "lfsd_trace_append")
 
     def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
                      eligible=None):
