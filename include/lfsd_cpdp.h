@@ -28,6 +28,8 @@
  *   lfsd_optimizer_step_rows / lfsd_lookahead_rows   the same update rules with the rule and its hyper-parameters PER ROW: the runs
  *                         of test/opt_methods_comparison.py and test/*_learning_rate_comparison.py as one batch (ABI 13)
  *   lfsd_trace_append     loss_trace / parameter_trace of lib/QuadAlgorithm.py:244-252, kept on the device (ABI 13)
+ *   lfsd_normal_matrix / lfsd_lm_step   no counterpart: a second-order outer update for the sum-of-squares loss of
+ *                         lib/QuadAlgorithm.py:616-639, where the reference has the five first-order rules (ABI 14)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 13
+#define LFSD_ABI_VERSION 14
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -60,6 +62,7 @@ extern "C" {
 #define LFSD_OPT_ADAM     2
 #define LFSD_OPT_NADAM    3
 #define LFSD_OPT_AMSGRAD  4
+#define LFSD_OPT_LM       5   /* Levenberg-Marquardt (ABI 14): not a code of lfsd_optimizer_step*, its update is lfsd_lm_step */
 
 typedef struct lfsd_model_info {
   int abi_version;
@@ -315,6 +318,48 @@ int lfsd_lookahead_rows(int dtype, int batch, int n_param, const int* method, co
 int lfsd_trace_append(int dtype, int batch, int n_param, int iter_idx, int capacity,
                       const void* loss, const void* grad, const void* theta, const int* row_active,
                       void* loss_trace, void* gnorm_trace, void* theta_trace, void* stream);
+
+/* ABI 14 -- a Levenberg-Marquardt outer update.  The default loss is a sum of squares, loss = sum_k |y(tau_k) - wp_k|^2, and the forward
+ * sweep returns dx/dtheta on the grid (auxX_grid): its linear interpolant at the waypoint times, restricted to the interface components,
+ * is the Jacobian J of the residuals; the fused gradient is J^T r ("no factor 2").  lfsd_normal_matrix forms the Gauss-Newton matrix
+ *   H[b][q1][q2] = sum_k sum_c X(tau_k)[q1][idx_c] X(tau_k)[q2][idx_c]            (= J^T J;  H [B][n_param][n_param])
+ * with X the LINEAR interpolant of auxX_grid [B][n_grid+1][n_param][n_state] (the dx/dtheta(tau) of the fused gradient and of
+ * lfsd_waypoint_vjp at either interpolation level), interval and fraction as in lfsd_sample_grid; horizon [B], taus [B][n_waypoints],
+ * iface_idx [n_iface] int32 (state components; the interface compiled into a library is not served).  Summed k ascending, then c
+ * ascending, by one thread per element of the lower triangle, which stores the element and its mirror image: both triangles hold the
+ * same bits; no atomics, a row's H is the same bits in any batch.  A NaN row of auxX_grid (a row the sweeps skipped) gives a NaN row
+ * of H and touches no other.  Small eigenvalues of H are directions of theta the waypoints do not pin down.
+ * LFSD_EINVAL: a NULL pointer, a non-positive size, n_grid < 1, H overlapping an input, an unknown dtype, more than 2^31-1 workgroups.
+ * iface_idx is a device array and the call reads nothing back: its range is checked ON THE DEVICE -- with an entry outside
+ * [0, n_state) the call returns 0 and writes no word of H. */
+int lfsd_normal_matrix(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                       const int* iface_idx, const void* horizon, const void* taus, const void* auxX_grid, void* H, void* stream);
+
+/* The accept / reject state machine of Levenberg-Marquardt and the damped solve, for every row, in one launch and without a host read.
+ * State per row (in/out):  theta [B][p] the last accepted point;  loss_acc [B], grad_acc [B][p], H_acc [B][p][p] loss, gradient and H
+ * there (loss_acc = +inf: nothing accepted yet);  lambda [B] the damping;  theta_trial [B][p]: on input the point that was just
+ * evaluated, on output the next point to evaluate.  Inputs: loss_t [B], grad_t [B][p], H_t [B][p][p] the evaluation at theta_trial;
+ * proj_lo [p] or NULL;  row_active [B] int32 or NULL (a row with 0 keeps every word of its state);  lambda_down / lambda_up /
+ * lambda_min / lambda_max, cast to `dtype`.  accepted [B] int32 or NULL: 1 where the row accepted in this call, else 0 (also for a
+ * row that is not active).  For every active row:
+ *   1. accept iff loss_t < loss_acc and loss_t, grad_t, H_t are all finite:  theta <- theta_trial, (loss, grad, H)_acc <- (loss, grad,
+ *      H)_t, lambda <- max(lambda * lambda_down, lambda_min);  otherwise lambda <- min(lambda * lambda_up, lambda_max);
+ *   2. loss_acc still +inf, or max_j H_acc[j][j] not positive:  theta_trial <- theta (the row cannot move);  else
+ *   3. A = H_acc + lambda (diag(H_acc) + 1e-8 max_j H_acc[j][j] I)  (Marquardt's scaling with a floor: a parameter without
+ *      sensitivity cannot make A singular),
+ *   4. Cholesky without pivoting, A delta = -grad_acc;
+ *   5. a pivot that is not positive or not finite:  lambda <- min(lambda * lambda_up, lambda_max) and the factorisation again, at most
+ *      8 such retries in one call (lambda is raised once per retry); if the last one fails too, theta_trial <- theta;
+ *   6. else theta_trial <- max(theta + delta, proj_lo) componentwise.
+ * One row per lane, fixed operation order, no atomics: a row's outputs are the same bits in any batch.
+ * The nine state / input arrays must be distinct and must not overlap (not checked).
+ * LFSD_EINVAL: a NULL required pointer, batch <= 0, n_param <= 0 or > 16, lambda_down outside (0, 1], lambda_up < 1, lambda_min <= 0
+ * or > lambda_max, a NaN among the four, any of these AFTER the cast to `dtype` (a lambda_min that is 0 as a float, a lambda_max that
+ * is inf), an unknown dtype. */
+int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down, double lambda_up, double lambda_min, double lambda_max,
+                 void* theta, void* loss_acc, void* grad_acc, void* H_acc, void* lambda, void* theta_trial,
+                 const void* loss_t, const void* grad_t, const void* H_t, const void* proj_lo, const int* row_active,
+                 int* accepted, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

@@ -664,12 +664,32 @@ class SparseDemoLearner:
     previous test: a seed is traced in the step in which it stops and never after -- its later entries stay NaN, as the reference's
     trace simply ends there (a row ``skip_unconverged`` froze for one step is traced: it repeats its theta).  A step beyond the
     capacity raises ``LfsdError``.  In ``shared`` mode the traces have the single row.
+
+    ``method="LM"`` (``independent`` mode, the fused loss): a Levenberg-Marquardt outer update where the reference has first-order rules
+    only.  The fused loss is a sum of squares and the forward sweep already returns dx/dtheta on the grid, so every evaluation also
+    writes the sensitivity grids and one more small launch (``lfsd_normal_matrix``) forms the Gauss-Newton matrix ``H = J^T J`` [B, p, p]
+    of the waypoint residuals, in the sweeps' dtype, cast to theta's as the gradient is.  ``lfsd_lm_step`` then, per row and without a
+    host read: accepts the evaluated point iff its loss is below the accepted one and loss, gradient and H are finite (the damping
+    ``lambda`` is multiplied by ``lm_down`` on acceptance, by ``lm_up`` on rejection, kept inside [``lm_min``, ``lm_max``]), and solves
+    ``(H + lambda (diag H + 1e-8 max diag H I)) delta = -grad`` at the accepted point for the next trial point (projected as ever).
+    Defaults ``lm_lambda0=1e-2, lm_down=1/3, lm_up=2, lm_min=1e-8, lm_max=1e8``: ordinary Marquardt values, nothing tuned.
+    ``theta`` is the ACCEPTED point; ``step()`` evaluates the trial point and returns its (loss, grad) -- the convention of Nesterov's
+    look-ahead point; the first finite evaluation (of theta_0) is always accepted.  ``lm_lambda`` [B], ``lm_loss`` [B] (the accepted
+    loss, +inf before the first acceptance; it never increases), ``lm_accepted`` [B] bool (the last step) and ``normal_matrix``
+    [B, p, p] (H at the accepted point: small eigenvalues are directions of theta the waypoints do not pin down) report the state.
+    It combines with ``stop_rule`` (the test reads the returned loss and gradient), ``warm_start``, ``skip_unconverged`` (a frozen row
+    keeps its whole LM state and evaluates the same trial point again -- so a row frozen by its sweeps' tolerance flag, not by an
+    unfinished solve, stays frozen: DESIGN.md section 14), ``interplation_level=2`` and ``trace`` (``theta_trace`` files
+    the accepted theta).  Refused with ``LfsdError``: ``loss_fn`` (a general loss is not a sum of squares), ``mode='shared'``, any
+    per-row argument or a ``method`` sequence containing "LM" (the rows path carries the five first-order rules), a model whose
+    interface function is compiled in (``interface_idx=None``: J would need the generated dg/dx), and more than 16 parameters.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
-                 skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None):
+                 skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None,
+                 lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
         if loss_fn is not None and not callable(loss_fn):
             raise LfsdError("loss_fn must be callable: loss_fn(x_tau [B,K,n], u_tau [B,K,m]) -> loss [B]")
@@ -684,6 +704,23 @@ class SparseDemoLearner:
         for mth in (list(method) if isinstance(method, (list, tuple, np.ndarray)) else [method]):
             if not isinstance(mth, str) or mth not in runtime.OPT_METHODS:
                 raise Exception("Wrong optimization method type!")
+        self._lm = None
+        if not isinstance(method, str) and "LM" in list(method):
+            raise LfsdError("method 'LM' in a per-row method list: the rows path carries the five first-order rules only "
+                            "(lfsd_optimizer_step_rows); give method='LM' for the whole batch")
+        if method == "LM":
+            if loss_fn is not None:
+                raise LfsdError("method='LM' needs the fused waypoint loss: a general loss_fn is not a sum of squares, so J^T J is not "
+                                "a model of it")
+            if mode != "independent":
+                raise LfsdError("method='LM' keeps a damping and an accepted point per seed: mode='independent' only")
+            if interface_idx is None:
+                raise LfsdError("method='LM' needs interface_idx: with the interface function compiled into the library the Jacobian "
+                                "of the residuals would need the generated dg/dx")
+            hp = dict(lambda0=float(lm_lambda0), down=float(lm_down), up=float(lm_up), lo=float(lm_min), hi=float(lm_max))
+            if not (0 < hp["down"] <= 1 and hp["up"] >= 1 and 0 < hp["lo"] <= hp["hi"] and hp["lo"] <= hp["lambda0"] <= hp["hi"]):
+                raise LfsdError("method='LM' needs 0 < lm_down <= 1 <= lm_up and 0 < lm_min <= lm_lambda0 <= lm_max (got %s)" % hp)
+            self._lm = hp
         self.mode, self.pg = mode, process_group
         self.lib = oc.compile()
         x0 = oc._t(ini_state)
@@ -719,6 +756,18 @@ class SparseDemoLearner:
         self.iter_idx = 0
         self.true_loss = true_loss_print_flag
         self._init_rows(method, learning_rate, mu, beta_1, beta_2, epsilon, true_loss_print_flag)
+        if self._lm is not None:
+            if self._rows_path:
+                raise LfsdError("method='LM' with a per-row argument: the rows path carries the five first-order rules only")
+            if p > 16:
+                raise LfsdError("method='LM' factors a p x p matrix per lane: n_auxvar = %d > 16" % p)
+            th, dev = self.theta, self.theta.device
+            self.theta_trial = th.clone()                     # the point step() evaluates next (theta: the accepted point)
+            self._lm.update(loss=torch.full((B,), float("inf"), dtype=th.dtype, device=dev), grad=torch.zeros_like(th),
+                            H=torch.zeros((B, p, p), dtype=th.dtype, device=dev),
+                            lam=torch.full((B,), self._lm["lambda0"], dtype=th.dtype, device=dev),
+                            accepted=torch.zeros(B, dtype=torch.int32, device=dev))
+            self._H_t = self._H_full = None
         self._init_trace(trace)
         # warm_start: start every OC solve from the previous iteration's controls (theta moves little per step).
         # The reference cold-starts IPOPT every time; the converged KKT point is the same, only the path to it is shorter.
@@ -816,14 +865,21 @@ class SparseDemoLearner:
 
     def _eval_point(self):
         """Where the update rules want loss and gradient: theta, or the Nesterov look-ahead point (QuadAlgorithm.py:478)."""
+        if self._lm is not None:
+            return self.theta_trial
         if not self._rows_path:
             return self.lib.lookahead(self.theta, self.m, self.mu) if self.method == "Nesterov" else self.theta
         if not self._any_nesterov:
             return self.theta
         return self.lib.lookahead_rows(self._method_rows, self._hyper, self.theta, self.m)
 
-    def _update(self, grad, row_active):
-        if not self._rows_path:
+    def _update(self, grad, row_active, loss=None):
+        if self._lm is not None:      # accept / reject the point just evaluated and solve for the next one (lfsd_lm_step)
+            s = self._lm
+            self.lib.lm_step(self.theta, s["loss"], s["grad"], s["H"], s["lam"], self.theta_trial, loss.contiguous(), grad.contiguous(),
+                             self._H_t, lambda_down=s["down"], lambda_up=s["up"], lambda_min=s["lo"], lambda_max=s["hi"],
+                             proj_lo=self.proj_lo, row_active=row_active, accepted=s["accepted"])
+        elif not self._rows_path:
             self.lib.optimizer_step(self.method, self.theta, grad, self.iter_idx, self.lr, self.mu, self.b1, self.b2, self.eps,
                                     m=self.m, v=self.v, vhat=self.vhat, proj_lo=self.proj_lo, row_active=row_active)
         else:
@@ -859,6 +915,21 @@ class SparseDemoLearner:
         if self._trace_cap is not None:
             self.lib.trace_append(self.iter_idx - 1, loss.contiguous(), grad.contiguous(), self.theta, loss_trace=self.loss_trace,
                                   gnorm_trace=self.grad_norm_trace, theta_trace=self.theta_trace, row_active=row_active)
+
+    def _normal_matrix(self, aux, hz, taus):
+        """H = J^T J [rows, p, p] of the evaluation `aux` (sensitivity grids written), in the sweeps' dtype, cast to theta's."""
+        aX = aux["auxX_grid"]
+        cv = lambda t: t.to(aX.dtype).contiguous()
+        return self.lib.normal_matrix(cv(hz), cv(taus), aX, self.iface).to(self.theta.dtype)
+
+    lm_lambda = property(lambda self: None if self._lm is None else self._lm["lam"], doc="[B] damping of every seed (method='LM')")
+    lm_loss = property(lambda self: None if self._lm is None else self._lm["loss"],
+                       doc="[B] loss at the accepted point, +inf before the first acceptance (method='LM')")
+    lm_accepted = property(lambda self: None if self._lm is None else self._lm["accepted"] != 0,
+                           doc="[B] bool: the seed accepted its trial point in the last step (method='LM')")
+    normal_matrix = property(lambda self: None if self._lm is None else self._lm["H"],
+                             doc="[B, p, p] Gauss-Newton matrix J^T J at the accepted point (method='LM'): small eigenvalues are "
+                                 "directions of theta the waypoints do not pin down")
 
     @property
     def active(self):
@@ -900,11 +971,16 @@ class SparseDemoLearner:
             return loss, grad
         # a learner that freezes unconverged rows anyway does not pay for differentiating them (they are masked by their
         # status below): the diverged seeds of a fixed learning rate otherwise hold the Riccati launch 20x longer
-        self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, Z_grid=self._Z,
+        lm = self._lm is not None                        # (LM: the sensitivity grids are written too, J^T J is formed from them)
+        self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, want_grids=lm, Z_grid=self._Z,
                                               out=self._aux_out(), phase_hook=phase, validate=False,
                                               skip_status=(3, 4) if self.skip_unconverged else None,
                                               interplation_level=self.interplation_level)
         self._Z = self._aux["Z_grid"]
+        if lm:
+            if hook is not None:
+                hook("normal_matrix")
+            self._H_t = self._normal_matrix(self._aux, self.hz, self.taus)
         loss, grad = self._aux["loss"].to(self.theta.dtype), self._aux["grad"].to(self.theta.dtype)
         if self.skip_unconverged:
             loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
@@ -1004,10 +1080,16 @@ class SparseDemoLearner:
                                                                           "iters", "status")})
         self._ws = sol["workspace"]
         phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
-        aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, Z_grid=full["Z"][:n],
+        lm = self._lm is not None
+        aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, want_grids=lm, Z_grid=full["Z"][:n],
                                         out={k: full["aux"][k][:n] for k in ("loss", "grad", "stats")}, phase_hook=phase,
                                         validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
                                         interplation_level=self.interplation_level)
+        if lm:      # H of the dense rows goes to its seeds' rows of the full-size matrix, as loss and gradient do
+            if hook is not None:
+                hook("normal_matrix")
+            lib.scatter_rows(rows, self._normal_matrix(aux, d["hz"][:n], d["taus"][:n]).contiguous(), self._H_full, n)
+            self._H_t = self._H_full
         self._sol_active, self._aux_active = sol, aux
         self._prev = (sol["control_grid"], sol["status"])
         loss, grad = aux["loss"].to(self.theta.dtype), aux["grad"].to(self.theta.dtype)
@@ -1029,6 +1111,8 @@ class SparseDemoLearner:
             return
         if self._dense is None:          # the first seeds stop: from here on the solver buffers hold a dense batch
             self._loss_full, self._grad_full = loss.clone(), grad.clone()
+            if self._lm is not None:
+                self._H_full = self._H_t.clone()
             self._full = dict(sol=self._sol_out(), aux=self._aux_out(), Z=self._Z)
             src = dict(x0=self.x0, hz=self.hz, taus=self.taus, wps=self.wps)
             if self.consts is not None and self.consts.dim() == 2:
@@ -1079,7 +1163,7 @@ class SparseDemoLearner:
             row_active = ok if n == B else lib.scatter_rows(self._rows[self._cur], ok, self._active.clone(), n)
             if self.count_unconverged:
                 self.n_unconverged = int(n - self._ok.sum().item())
-        self._update(grad_full, row_active)
+        self._update(grad_full, row_active, loss_full)
         self.iter_idx += 1
         if hook is not None:
             hook("end")
@@ -1132,7 +1216,7 @@ class SparseDemoLearner:
                 row_active = self._ok.to(torch.int32)
                 if self.count_unconverged:
                     self.n_unconverged = int(self.B - self._ok.sum().item())
-        self._update(grad_used, row_active)
+        self._update(grad_used, row_active, loss_out)
         self.iter_idx += 1
         if hook is not None:
             hook("end")

@@ -98,12 +98,14 @@ class QuadAlgorithm(object):
         self.oc.setDevice(self.device, self.dtype)
         self.interface_pos_idx = [0, 1, 2]
         self.interface_ori_idx = [6, 7, 8, 9]
-        if self.optimization_method_str not in ("Vanilla", "Nesterov", "Adam", "Nadam", "AMSGrad"):
+        if self.optimization_method_str not in ("Vanilla", "Nesterov", "Adam", "Nadam", "AMSGrad", "LM"):
             raise Exception("Wrong optimization method type!")
 
     def load_optimization_function(self, para_input):
-        """QuadAlgorithm.py:133-191 (same dictionary keys)."""
-        self.learning_rate = para_input["learning_rate"]
+        """QuadAlgorithm.py:133-191 (same dictionary keys).  Beyond the reference: ``{"method": "LM", "iter_num": ...}`` with the
+        optional keys ``lm_lambda0``, ``lm_down``, ``lm_up``, ``lm_min``, ``lm_max`` of ``SparseDemoLearner`` (Levenberg-Marquardt has no
+        learning rate: ``learning_rate`` may be left out)."""
+        self.learning_rate = para_input.get("learning_rate", 0.0) if para_input["method"] == "LM" else para_input["learning_rate"]
         self.iter_num = para_input["iter_num"]
         self.optimization_method_str = para_input["method"]
         self.opt_kwargs = {}
@@ -117,6 +119,8 @@ class QuadAlgorithm(object):
         elif m in ("Adam", "Nadam", "AMSGrad"):
             self.opt_kwargs = dict(beta_1=para_input["beta_1"], beta_2=para_input["beta_2"],
                                    epsilon=para_input["epsilon"])
+        elif m == "LM":
+            self.opt_kwargs = {k: para_input[k] for k in ("lm_lambda0", "lm_down", "lm_up", "lm_min", "lm_max") if k in para_input}
         else:
             raise Exception("Wrong optimization method type!")
 

@@ -696,3 +696,52 @@ LFSD_API int lfsd_trace_append(int dtype, int batch, int n_param, int iter_idx, 
   }
   return LFSD_EINVAL;
 }
+
+// ---- ABI 14: Levenberg-Marquardt outer update from per-seed Gauss-Newton matrices (cpdp_lm.h; no counterpart in the reference) ----
+LFSD_API int lfsd_normal_matrix(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                const int* iface_idx, const void* horizon, const void* taus, const void* auxX_grid, void* H,
+                                void* stream) {
+  if (batch <= 0 || n_grid < 1 || n_state <= 0 || n_param <= 0 || n_waypoints <= 0 || n_iface <= 0) return LFSD_EINVAL;
+  if (!iface_idx || !horizon || !taus || !auxX_grid || !H) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, P = (unsigned long long)n_param;
+  const unsigned long long hb = B * P * P * es;
+  if (spans_overlap(H, hb, iface_idx, (unsigned long long)n_iface * sizeof(int)) || spans_overlap(H, hb, horizon, B * es) ||
+      spans_overlap(H, hb, taus, B * n_waypoints * es) ||
+      spans_overlap(H, hb, auxX_grid, B * (unsigned long long)(n_grid + 1) * P * n_state * es))
+    return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::NormalMatrixArgs<float> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const float*)horizon,
+                                    (const float*)taus, (const float*)auxX_grid, (float*)H};
+    return lfsd_detail::launch_normal_matrix_f32(a, stream);
+  }
+  lfsd::NormalMatrixArgs<double> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const double*)horizon,
+                                   (const double*)taus, (const double*)auxX_grid, (double*)H};
+  return lfsd_detail::launch_normal_matrix_f64(a, stream);
+}
+
+LFSD_API int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down, double lambda_up, double lambda_min,
+                          double lambda_max, void* theta, void* loss_acc, void* grad_acc, void* H_acc, void* lambda,
+                          void* theta_trial, const void* loss_t, const void* grad_t, const void* H_t, const void* proj_lo,
+                          const int* row_active, int* accepted, void* stream) {
+  if (batch <= 0 || n_param <= 0 || n_param > lfsd::LM_MAX_PARAM) return LFSD_EINVAL;
+  if (!theta || !loss_acc || !grad_acc || !H_acc || !lambda || !theta_trial || !loss_t || !grad_t || !H_t) return LFSD_EINVAL;
+  // (every comparison is false for a NaN: written so that a NaN scalar fails one of them)
+  if (!(lambda_down > 0 && lambda_down <= 1) || !(lambda_up >= 1) || !(lambda_min > 0) || !(lambda_min <= lambda_max)) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    // the same conditions on the values the kernel gets: 1e-50 is positive as a double and 0 as a float, and a damping of 0 stays 0
+    const float dn = (float)lambda_down, up = (float)lambda_up, lo = (float)lambda_min, hi = (float)lambda_max;
+    if (!(dn > 0 && dn <= 1) || !(up >= 1) || !(lo > 0) || !(lo <= hi) || !(hi <= 3.0e38f)) return LFSD_EINVAL;
+    lfsd::LmStepArgs<float> a{batch, n_param, (float)lambda_down, (float)lambda_up, (float)lambda_min, (float)lambda_max,
+                              (float*)theta, (float*)loss_acc, (float*)grad_acc, (float*)H_acc, (float*)lambda, (float*)theta_trial,
+                              (const float*)loss_t, (const float*)grad_t, (const float*)H_t, (const float*)proj_lo, row_active, accepted};
+    return lfsd_detail::launch_lm_step_f32(a, stream);
+  }
+  if (dtype == LFSD_F64) {
+    lfsd::LmStepArgs<double> a{batch, n_param, lambda_down, lambda_up, lambda_min, lambda_max,
+                               (double*)theta, (double*)loss_acc, (double*)grad_acc, (double*)H_acc, (double*)lambda, (double*)theta_trial,
+                               (const double*)loss_t, (const double*)grad_t, (const double*)H_t, (const double*)proj_lo, row_active, accepted};
+    return lfsd_detail::launch_lm_step_f64(a, stream);
+  }
+  return LFSD_EINVAL;
+}

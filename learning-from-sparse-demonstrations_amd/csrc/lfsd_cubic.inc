@@ -1,5 +1,6 @@
 // Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
-// the sampling kernels (ABI 12: cpdp_sample.h).  They live
+// the sampling kernels (ABI 12: cpdp_sample.h), the per-row rules (ABI 13: cpdp_opt.h) and the Levenberg-Marquardt kernels (ABI 14:
+// cpdp_lm.h).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -93,4 +94,25 @@ template <typename T> static int launch_trace_append(const lfsd::TraceArgs<T>& a
 }
 int launch_trace_append_f32(const lfsd::TraceArgs<float>& a, void* stream) { return launch_trace_append<float>(a, stream); }
 int launch_trace_append_f64(const lfsd::TraceArgs<double>& a, void* stream) { return launch_trace_append<double>(a, stream); }
+// ---- ABI 14: Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step (cpdp_lm.h) ----
+// one thread per (row, q1, q2): batch and n_param are positive ints, n_param^2 * batch stays below 2^62 in 64 bits only while
+// n_param < 2^15.5 -- larger ones are refused with the workgroup count
+template <typename T> static int launch_normal_matrix(const lfsd::NormalMatrixArgs<T>& a, void* stream) {
+  if (a.n_param > 46340) return LFSD_EINVAL;
+  const long long threads = (long long)a.batch * a.n_param * a.n_param;
+  const long long blocks = (threads + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::normal_matrix_kernel<T>), (unsigned)blocks, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_normal_matrix_f32(const lfsd::NormalMatrixArgs<float>& a, void* stream) { return launch_normal_matrix<float>(a, stream); }
+int launch_normal_matrix_f64(const lfsd::NormalMatrixArgs<double>& a, void* stream) { return launch_normal_matrix<double>(a, stream); }
+// one row per lane, one wavefront per workgroup (batch is a positive int: at most 2^25 workgroups)
+template <typename T> static int launch_lm_step(const lfsd::LmStepArgs<T>& a, void* stream) {
+  const unsigned grid = (unsigned)(((long long)a.batch + lfsd::LM_BLOCK - 1) / lfsd::LM_BLOCK);
+  LFSD_LAUNCH((lfsd::lm_step_kernel<T>), grid, lfsd::LM_BLOCK, stream, a);
+  return launch_status();
+}
+int launch_lm_step_f32(const lfsd::LmStepArgs<float>& a, void* stream) { return launch_lm_step<float>(a, stream); }
+int launch_lm_step_f64(const lfsd::LmStepArgs<double>& a, void* stream) { return launch_lm_step<double>(a, stream); }
 }

@@ -83,4 +83,9 @@ int launch_lookahead_rows_f32(const lfsd::LookaheadRowsArgs<float>& a, void* str
 int launch_lookahead_rows_f64(const lfsd::LookaheadRowsArgs<double>& a, void* stream);
 int launch_trace_append_f32(const lfsd::TraceArgs<float>& a, void* stream);
 int launch_trace_append_f64(const lfsd::TraceArgs<double>& a, void* stream);
+// Gauss-Newton matrix of the waypoint loss and the Levenberg-Marquardt step (ABI 14, cpdp_lm.h; the same third unit)
+int launch_normal_matrix_f32(const lfsd::NormalMatrixArgs<float>& a, void* stream);
+int launch_normal_matrix_f64(const lfsd::NormalMatrixArgs<double>& a, void* stream);
+int launch_lm_step_f32(const lfsd::LmStepArgs<float>& a, void* stream);
+int launch_lm_step_f64(const lfsd::LmStepArgs<double>& a, void* stream);
 }

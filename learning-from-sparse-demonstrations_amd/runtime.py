@@ -19,7 +19,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(PKG_DIR), "include")
 
 LFSD_F32, LFSD_F64 = 0, 1
 STATUS = {1: "converged", 2: "stalled", 3: "maxiter", 4: "failed"}
-OPT_METHODS = {"Vanilla": 0, "Nesterov": 1, "Adam": 2, "Nadam": 3, "AMSGrad": 4}
+OPT_METHODS = {"Vanilla": 0, "Nesterov": 1, "Adam": 2, "Nadam": 3, "AMSGrad": 4, "LM": 5}
 MAPPINGS = {"auto": 0, "lockstep": 1, "wide": 2}
 
 
@@ -106,7 +106,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
                   "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
@@ -274,7 +274,7 @@ class ModelLibrary:
                "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
                "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
-               "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append")
+               "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -312,12 +312,14 @@ class ModelLibrary:
         L.lfsd_optimizer_step_rows.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_lookahead_rows.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_trace_append.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.lfsd_normal_matrix.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.lfsd_lm_step.argtypes = [ci, ci, ci, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 13:
+        if rc != 0 or info.abi_version != 14:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -716,6 +718,67 @@ class ModelLibrary:
                                             self._p(row_active), self._p(loss_trace), self._p(gnorm_trace), self._p(theta_trace),
                                             self._stream(theta))
         self._rc(rc, "lfsd_trace_append")
+
+    # ---- ABI 14: Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step --------------------------------------------
+    def normal_matrix(self, horizon, taus, auxX_grid, iface_idx, out=None):
+        """H [B, p, p] = J^T J of the waypoint residuals (include/lfsd_cpdp.h, ABI 14): J is the linear interpolant of ``auxX_grid``
+        [B, n_grid+1, p, n] at ``taus`` [B, K], restricted to the state components ``iface_idx`` [n_iface] int32.  horizon [B].
+        Exactly symmetric; fixed summation order: a row's H is the same bits in any batch.  An entry of ``iface_idx`` outside
+        [0, n) is found on the device (nothing is read back here): the call then writes nothing.  Small eigenvalues of H are
+        directions of theta the waypoints do not pin down."""
+        if not isinstance(auxX_grid, torch.Tensor) or auxX_grid.dim() != 4:
+            raise LfsdError("auxX_grid must be a [B, n_grid+1, n_param, n_state] tensor")
+        if auxX_grid.dtype not in _DT:
+            raise LfsdError("auxX_grid has dtype %s: float32 or float64" % auxX_grid.dtype)
+        dt = auxX_grid.dtype
+        B, N1, p, n = auxX_grid.shape
+        if not isinstance(taus, torch.Tensor) or taus.dim() != 2 or taus.shape[1] < 1:
+            raise LfsdError("taus must be a [B, K] tensor with K >= 1")
+        if not isinstance(iface_idx, torch.Tensor) or iface_idx.dim() != 1 or iface_idx.shape[0] < 1:
+            raise LfsdError("iface_idx must be an int32 tensor of at least one state component")
+        K, ni = taus.shape[1], iface_idx.shape[0]
+        self._check(auxX_grid, (B, N1, p, n), dt, "auxX_grid")
+        self._check(horizon, (B,), dt, "horizon")
+        self._check(taus, (B, K), dt, "taus")
+        self._check(iface_idx, (ni,), torch.int32, "iface_idx")
+        if N1 < 2:
+            raise LfsdError("n_grid = %d: the interpolant needs two nodes" % (N1 - 1))
+        if out is None:
+            out = torch.empty((B, p, p), dtype=dt, device=auxX_grid.device)
+        self._check(out, (B, p, p), dt, "out")
+        with self._on(auxX_grid):
+            rc = self.lib.lfsd_normal_matrix(_DT[dt], B, N1 - 1, n, p, K, ni, self._p(iface_idx), self._p(horizon), self._p(taus),
+                                             self._p(auxX_grid), self._p(out), self._stream(auxX_grid))
+        self._rc(rc, "lfsd_normal_matrix")
+        return out
+
+    def lm_step(self, theta, loss_acc, grad_acc, H_acc, lam, theta_trial, loss_t, grad_t, H_t, lambda_down=1.0 / 3.0, lambda_up=2.0,
+                lambda_min=1e-8, lambda_max=1e8, proj_lo=None, row_active=None, accepted=None):
+        """One Levenberg-Marquardt update of every row, in place (include/lfsd_cpdp.h, ABI 14): accept or reject the evaluation
+        (loss_t [B], grad_t [B, p], H_t [B, p, p]) of ``theta_trial``, adapt ``lam`` [B], and leave in ``theta_trial`` the next
+        point to evaluate.  theta / grad_acc [B, p], loss_acc [B] (+inf: nothing accepted yet), H_acc [B, p, p]; p <= 16.
+        ``accepted`` [B] int32 or None.  Nothing is read back."""
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.dtype not in _DT:
+            raise LfsdError("theta must be a [B, n_param] float32 / float64 tensor")
+        B, p = theta.shape
+        dt = theta.dtype
+        if p > 16:
+            raise LfsdError("lm_step factors a p x p matrix per lane: n_param = %d > 16" % p)
+        for nm, t in (("theta", theta), ("grad_acc", grad_acc), ("theta_trial", theta_trial), ("grad_t", grad_t)):
+            self._check(t, (B, p), dt, nm)
+        for nm, t in (("loss_acc", loss_acc), ("lambda", lam), ("loss_t", loss_t)):
+            self._check(t, (B,), dt, nm)
+        for nm, t in (("H_acc", H_acc), ("H_t", H_t)):
+            self._check(t, (B, p, p), dt, nm)
+        self._check(proj_lo, (p,), dt, "proj_lo", optional=True)
+        self._check(row_active, (B,), torch.int32, "row_active", optional=True)
+        self._check(accepted, (B,), torch.int32, "accepted", optional=True)
+        with self._on(theta):
+            rc = self.lib.lfsd_lm_step(_DT[dt], B, p, float(lambda_down), float(lambda_up), float(lambda_min), float(lambda_max),
+                                       self._p(theta), self._p(loss_acc), self._p(grad_acc), self._p(H_acc), self._p(lam),
+                                       self._p(theta_trial), self._p(loss_t), self._p(grad_t), self._p(H_t), self._p(proj_lo),
+                                       self._p(row_active), self._p(accepted), self._stream(theta))
+        self._rc(rc, "lfsd_lm_step")
 
     def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
                      eligible=None):
