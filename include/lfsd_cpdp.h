@@ -30,6 +30,8 @@
  *   lfsd_trace_append     loss_trace / parameter_trace of lib/QuadAlgorithm.py:244-252, kept on the device (ABI 13)
  *   lfsd_normal_matrix / lfsd_lm_step   no counterpart: a second-order outer update for the sum-of-squares loss of
  *                         lib/QuadAlgorithm.py:616-639, where the reference has the five first-order rules (ABI 14)
+ *   lfsd_group_reduce     no counterpart: the reference learns from one demonstration per run (lib/QuadAlgorithm.py:239-257); loss,
+ *                         gradient and J^T J of several demonstrations per seed, summed per seed in a fixed order (ABI 15)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -38,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 14
+#define LFSD_ABI_VERSION 15
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -360,6 +362,25 @@ int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down, double l
                  void* theta, void* loss_acc, void* grad_acc, void* H_acc, void* lambda, void* theta_trial,
                  const void* loss_t, const void* grad_t, const void* H_t, const void* proj_lo, const int* row_active,
                  int* accepted, void* stream);
+
+/* ABI 15 -- several demonstrations per seed.  A batch of B = n_groups * group_size rows holds the demonstrations of one seed (one
+ * parameter vector) next to each other: row g * group_size + d is demonstration d of group g.  The solve, the sweeps and
+ * lfsd_normal_matrix run on the B rows as ever (the parameters of the groups are expanded to rows with lfsd_gather_rows and the index
+ * row -> row / group_size); this call sums their results per group, and the update entry points then run on n_groups rows unchanged.
+ * J^T J of the stacked residuals of a group is the sum of its rows' matrices.
+ *   loss [B], grad [B][n_param], H [B][n_param][n_param] or NULL;  row_ok [B] int32 or NULL (= every row counts)
+ *   loss_g [G], grad_g [G][n_param], H_g [G][n_param][n_param] or NULL (given exactly when H is);  n_ok [G] int32
+ * For every group and every element (the loss, the n_param gradient components, the n_param^2 entries of H) the output is 0 of type
+ * `dtype` plus the values of the rows with row_ok != 0, added one at a time, demonstrations ascending, in that type.  The values of a
+ * row that is left out are never added (nor read): they may be NaN.  A NaN in a row that counts propagates to its group and to no
+ * other.  n_ok[g] is the number of rows counted; a group with n_ok == 0 gets zeros.  One thread per (group, element), no atomics, one
+ * summation order: a group's outputs are the same bits in any batch and at any position in it, and H_g is as bit-symmetric as its
+ * inputs.
+ * LFSD_EINVAL, before any launch: n_groups, group_size or n_param <= 0, an unknown dtype, a NULL required pointer, exactly one of H and
+ * H_g given, an output overlapping an input, more than 2^31-1 workgroups. */
+int lfsd_group_reduce(int dtype, int n_groups, int group_size, int n_param,
+                      const void* loss, const void* grad, const void* H, const int* row_ok,
+                      void* loss_g, void* grad_g, void* H_g, int* n_ok, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

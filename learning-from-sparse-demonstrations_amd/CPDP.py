@@ -683,14 +683,52 @@ class SparseDemoLearner:
     the accepted theta).  Refused with ``LfsdError``: ``loss_fn`` (a general loss is not a sum of squares), ``mode='shared'``, any
     per-row argument or a ``method`` sequence containing "LM" (the rows path carries the five first-order rules), a model whose
     interface function is compiled in (``interface_idx=None``: J would need the generated dg/dx), and more than 16 parameters.
+
+    ``mode='grouped', demos_per_seed=D``: G seeds (or configurations) that each learn from the same D demonstrations, B = G * D rows,
+    row ``g * D + d`` = demonstration d of group g (``n_groups``, ``demos_per_seed``).  ``ini_state`` / ``horizon`` / ``taus`` /
+    ``waypoints`` may be given per demonstration (leading dimension D: tiled over the groups), per row (B) or broadcast as ever;
+    ``theta0`` is [p], [1, p] or [G, p].  ``theta``, ``m``, ``v``, ``vhat``, the LM state and the traces have G rows.  One step: the
+    evaluation point on G rows, ``lfsd_gather_rows`` to [B, p], the solve and both sweeps (and ``lfsd_normal_matrix``) on B rows as
+    ``evaluate()`` runs them in the other modes, ``lfsd_group_reduce`` -- per group 0 plus its rows' loss, gradient and H, added in
+    ascending order on the device, the same bits in any batch -- and the unchanged update kernel on G rows.  ``step()`` and
+    ``evaluate(theta [G, p])`` return the group sums (loss [G], grad [G, p]); ``row_loss`` [B] / ``row_grad`` [B, p] hold the last
+    per-demonstration values, ``n_ok`` [G] int32 (a device tensor) the demonstrations that entered each sum.  ``skip_unconverged``
+    defaults to ON, as in shared mode (one bad demonstration would poison a sum): the mask of ``mask_unconverged`` is the kernel's
+    ``row_ok``, a group with ``n_ok == 0`` is masked out of the update (parameters, optimizer and LM state keep every word), and
+    ``n_unconverged`` counts the rows left out (read only with ``count_unconverged``).  Update rules: the five uniform ones, the rows
+    path with sequences of length G, and ``method='LM'`` with H_g the sum of the demonstrations' H (``normal_matrix`` [G, p, p]).  It
+    combines with ``warm_start`` (controls stay per row), ``interplation_level=2``, ``loss_fn`` (which sees all B rows), ``trace``
+    (G rows) and a scalar ``true_loss_print_flag`` (a second evaluation, reduced as the first).  ``event_hook`` gets one more phase,
+    "group_reduce".  Refused with ``LfsdError``: ``stop_rule`` (dense-batch bookkeeping per group), a ``process_group`` or an
+    initialised ``torch.distributed`` (no all-reduce is issued), a sequence for ``true_loss_print_flag``, a batch that is no whole
+    number of groups, ``demos_per_seed`` with another mode, a ``theta0`` or per-group sequence of the wrong length (DESIGN.md
+    section 15).
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
                  skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None,
-                 lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8):
+                 lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8, demos_per_seed=None):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
+        self.demos_per_seed = self.n_groups = None
+        if demos_per_seed is not None and mode != "grouped":
+            raise LfsdError("demos_per_seed belongs to mode='grouped' (mode=%r gives every row %s)"
+                            % (mode, "the one theta" if mode == "shared" else "its own theta and one demonstration"))
+        if mode == "grouped":
+            D = demos_per_seed
+            if D is None or isinstance(D, bool) or int(D) != D or int(D) <= 0:
+                raise LfsdError("mode='grouped' needs demos_per_seed, a positive number of demonstrations per seed (got %r)" % (D,))
+            self.demos_per_seed = int(D)
+            if stop_rule is not None:
+                raise LfsdError("stop_rule does not combine with mode='grouped' yet: the dense batch would have to keep whole groups "
+                                "together (bookkeeping per group)")
+            if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
+                raise LfsdError("mode='grouped' issues no all-reduce: a process_group or an initialised torch.distributed would be "
+                                "ignored silently (every rank learns its own groups)")
+            if self._per_row(true_loss_print_flag) is not None:
+                raise LfsdError("true_loss_print_flag per group: mode='grouped' takes a scalar flag (the second evaluation is reduced "
+                                "for every group or for none)")
         if loss_fn is not None and not callable(loss_fn):
             raise LfsdError("loss_fn must be callable: loss_fn(x_tau [B,K,n], u_tau [B,K,m]) -> loss [B]")
         if loss_fn is not None and stop_rule is not None:
@@ -712,8 +750,8 @@ class SparseDemoLearner:
             if loss_fn is not None:
                 raise LfsdError("method='LM' needs the fused waypoint loss: a general loss_fn is not a sum of squares, so J^T J is not "
                                 "a model of it")
-            if mode != "independent":
-                raise LfsdError("method='LM' keeps a damping and an accepted point per seed: mode='independent' only")
+            if mode not in ("independent", "grouped"):
+                raise LfsdError("method='LM' keeps a damping and an accepted point per seed: mode='independent' (or 'grouped') only")
             if interface_idx is None:
                 raise LfsdError("method='LM' needs interface_idx: with the interface function compiled into the library the Jacobian "
                                 "of the residuals would need the generated dg/dx")
@@ -723,6 +761,8 @@ class SparseDemoLearner:
             self._lm = hp
         self.mode, self.pg = mode, process_group
         self.lib = oc.compile()
+        if mode == "grouped":
+            ini_state, horizon, taus, waypoints = self._tile_demonstrations(ini_state, horizon, taus, waypoints, theta0)
         x0 = oc._t(ini_state)
         self.x0 = x0.unsqueeze(0) if x0.dim() == 1 else x0
         B = self.B = self.x0.shape[0]
@@ -744,6 +784,18 @@ class SparseDemoLearner:
         if mode == "shared":
             assert th.shape[0] == 1, "shared mode keeps a single parameter vector"
             self.theta = th.clone()
+        elif mode == "grouped":
+            G = self.n_groups
+            if th.dim() != 2 or th.shape[0] not in (1, G) or th.shape[1] != p:
+                raise LfsdError("theta0 has shape %s for %d groups of %d demonstrations: [p], [1, p] or [G, p] with p = %d"
+                                % (tuple(th.shape), G, self.demos_per_seed, p))
+            self.theta = th.expand(G, p).contiguous().clone()
+            dev = self.x0.device
+            # row -> its group, built once: lfsd_gather_rows expands the evaluation point [G, p] to the rows [B, p]
+            self._group_of_row = (torch.arange(B, dtype=torch.int32, device=dev) // self.demos_per_seed).contiguous()
+            self._theta_rows = torch.empty((B, p), dtype=self.theta.dtype, device=dev)
+            self._grp_out = None
+            self.row_loss = self.row_grad = self.n_ok = None
         else:
             self.theta = th.expand(B, p).contiguous().clone()
         self.consts = consts if consts is not None else oc.consts_tensor()
@@ -762,17 +814,18 @@ class SparseDemoLearner:
             if p > 16:
                 raise LfsdError("method='LM' factors a p x p matrix per lane: n_auxvar = %d > 16" % p)
             th, dev = self.theta, self.theta.device
+            R = th.shape[0]                                   # rows of parameters: B, or the groups of mode='grouped'
             self.theta_trial = th.clone()                     # the point step() evaluates next (theta: the accepted point)
-            self._lm.update(loss=torch.full((B,), float("inf"), dtype=th.dtype, device=dev), grad=torch.zeros_like(th),
-                            H=torch.zeros((B, p, p), dtype=th.dtype, device=dev),
-                            lam=torch.full((B,), self._lm["lambda0"], dtype=th.dtype, device=dev),
-                            accepted=torch.zeros(B, dtype=torch.int32, device=dev))
+            self._lm.update(loss=torch.full((R,), float("inf"), dtype=th.dtype, device=dev), grad=torch.zeros_like(th),
+                            H=torch.zeros((R, p, p), dtype=th.dtype, device=dev),
+                            lam=torch.full((R,), self._lm["lambda0"], dtype=th.dtype, device=dev),
+                            accepted=torch.zeros(R, dtype=torch.int32, device=dev))
             self._H_t = self._H_full = None
         self._init_trace(trace)
         # warm_start: start every OC solve from the previous iteration's controls (theta moves little per step).
         # The reference cold-starts IPOPT every time; the converged KKT point is the same, only the path to it is shorter.
         self.warm_start = warm_start
-        self.skip_unconverged = (mode == "shared") if skip_unconverged is None else bool(skip_unconverged)
+        self.skip_unconverged = (mode in ("shared", "grouped")) if skip_unconverged is None else bool(skip_unconverged)
         self.count_unconverged = True      # one small device->host read per step; switch off inside timed loops
         self.n_unconverged = 0
         self.n_bad_device = None
@@ -817,7 +870,7 @@ class SparseDemoLearner:
         return None
 
     def _init_rows(self, method, learning_rate, mu, beta_1, beta_2, epsilon, true_loss):
-        B, dev = self.B, self.x0.device
+        B, dev = (self.n_groups if self.mode == "grouped" else self.B), self.x0.device      # (rows of parameters)
         seqs = dict(method=list(method) if isinstance(method, (list, tuple, np.ndarray)) else None, learning_rate=self._per_row(learning_rate),
                     mu=self._per_row(mu), beta_1=self._per_row(beta_1), beta_2=self._per_row(beta_2), epsilon=self._per_row(epsilon),
                     true_loss_print_flag=self._per_row(true_loss))
@@ -829,7 +882,7 @@ class SparseDemoLearner:
                             % ", ".join(k for k, v in seqs.items() if v is not None))
         for k, v in seqs.items():
             if v is not None and len(v) != B:
-                raise LfsdError("%s has %d entries for a batch of %d rows" % (k, len(v), B))
+                raise LfsdError("%s has %d entries for a batch of %d %s" % (k, len(v), B, "groups" if self.mode == "grouped" else "rows"))
         full = lambda v, scalar: [scalar] * B if v is None else v
         methods = full(seqs["method"], method)
         codes = np.array([runtime.OPT_METHODS[mth] for mth in methods], dtype=np.int32)
@@ -946,7 +999,13 @@ class SparseDemoLearner:
         return self._stop_iter
 
     def evaluate(self, theta):
-        """(loss [B], grad [B,p]) of every trajectory at parameters theta ([B,p] or [1,p])."""
+        """(loss [B], grad [B,p]) of every trajectory at parameters theta ([B,p] or [1,p]).  mode='grouped': the group sums
+        (loss [G], grad [G,p]) at theta [G,p] or [1,p]; any other shape is refused."""
+        if self.mode == "grouped":
+            return self._evaluate_grouped(theta)
+        return self._evaluate_rows(theta)
+
+    def _evaluate_rows(self, theta):
         th = theta if theta.shape[0] == self.B else theta.expand(self.B, -1).contiguous()
         u_init = None
         if self.warm_start and self._sol is not None:
@@ -1186,8 +1245,96 @@ class SparseDemoLearner:
             return self._loss_full, self._grad_full
         return loss_full, grad_full
 
+    # ---- several demonstrations per seed (mode='grouped') -----------------------------------------------------------------
+    def _tile_demonstrations(self, ini_state, horizon, taus, waypoints, theta0):
+        """The four per-row inputs with B = G * D rows (row g * D + d: demonstration d of group g).  Each may come per demonstration
+        (leading dimension D: tiled over the groups), per row (B), or broadcast as in the other modes.  B is the largest leading
+        dimension given, at least D and at least D times the rows of theta0."""
+        oc, D = self.oc, self.demos_per_seed
+        # (name, tensor, dimensions of ONE row's value)
+        items = [("ini_state", oc._t(ini_state), 1), ("horizon", oc._t(horizon), 0), ("taus", oc._t(taus), 1),
+                 ("waypoints", None if waypoints is None else oc._t(waypoints), 2)]
+        th = oc._t(theta0)
+        lead = [t.shape[0] for _, t, nd in items if t is not None and t.dim() == nd + 1]
+        B = max(lead + [D, D * (th.shape[0] if th.dim() == 2 else 1)])
+        if B % D != 0:
+            raise LfsdError("a batch of %d rows is not a whole number of groups of demos_per_seed = %d" % (B, D))
+        G = self.n_groups = B // D
+        out = []
+        for name, t, nd in items:
+            if t is None or t.dim() == nd:                     # broadcast (the constructor expands it to the rows)
+                out.append(t)
+                continue
+            if t.dim() != nd + 1 or t.shape[0] not in (D, B):
+                raise LfsdError("%s has shape %s: per demonstration (%d rows), per row (%d = %d groups x %d) or one value for all"
+                                % (name, tuple(t.shape), D, B, G, D))
+            out.append(t if t.shape[0] == B else t.repeat((G,) + (1,) * nd).contiguous())
+        if out[0].dim() == 1:                                  # (the batch size is read from ini_state)
+            out[0] = out[0].unsqueeze(0).expand(B, -1).contiguous()
+        return out
+
+    def _evaluate_grouped(self, theta):
+        """(loss [G], grad [G,p]): theta [G,p] expanded to the rows, the B rows evaluated as ever, their results summed per group
+        (lfsd_group_reduce: 0 plus the rows mask_unconverged left ok, ascending).  With method='LM' the group's H too."""
+        lib, D = self.lib, self.demos_per_seed
+        G, p = self.theta.shape
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] != p or theta.shape[0] not in (1, G) \
+                or theta.dtype != self.theta.dtype:
+            raise LfsdError("mode='grouped' evaluates theta [%d, %d] (or [1, %d], expanded to the groups) of dtype %s, got %s"
+                            % (G, p, p, self.theta.dtype, (tuple(theta.shape), theta.dtype) if isinstance(theta, torch.Tensor) else type(theta)))
+        if theta.shape[0] != G:      # (the index row -> row // D reaches G - 1: the gather must find G rows)
+            theta = theta.expand(G, p)
+        th = lib.gather_rows(self._group_of_row, theta.contiguous(), self._theta_rows, self.B)
+        self._ok = None
+        loss, grad = self._evaluate_rows(th)
+        self.row_loss, self.row_grad = loss, grad
+        if self.event_hook is not None:
+            self.event_hook("group_reduce")
+        row_ok = None if self._ok is None else self._ok.to(torch.int32)
+        H = self._H_t.contiguous() if self._lm is not None else None
+        if self._grp_out is None:
+            G, p, dt, dev = self.n_groups, grad.shape[1], self.theta.dtype, self.theta.device
+            new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
+            self._grp_out = (new(G), new(G, p), None if H is None else new(G, p, p), torch.empty(G, dtype=torch.int32, device=dev))
+        loss_g, grad_g, H_g, self.n_ok = lib.group_reduce(loss.contiguous(), grad.contiguous(), D, H=H, row_ok=row_ok, out=self._grp_out)
+        if H_g is not None:
+            self._H_rows, self._H_t = self._H_t, H_g      # (what lfsd_lm_step reads: the group's J^T J)
+        return loss_g, grad_g
+
+    def _step_grouped(self):
+        """step() of mode='grouped': evaluation point on G rows, evaluation and reduction (above), update on G rows."""
+        self._check_trace_room()
+        theta_eval = self._eval_point()
+        loss, grad = self._evaluate_grouped(theta_eval)
+        hook = self.event_hook
+        if hook is not None:
+            hook("update")
+        row_active = None
+        if self._ok is not None:      # skip_unconverged: a group none of whose demonstrations counted keeps every word of its state
+            row_active = (self.n_ok > 0).to(torch.int32)
+            if self.count_unconverged:
+                self.n_unconverged = int(self.B - self.n_ok.sum().item())
+        self._update(grad, row_active, loss)
+        self.iter_idx += 1
+        if hook is not None:
+            hook("end")
+        second = self._true_rows is not None if self._rows_path else (self.method == "Nesterov" and bool(self.true_loss))
+        if second:                    # QuadAlgorithm.py:487-492: a second evaluation at theta, then reduced as the first
+            if not self._rows_path:
+                loss, grad = self._evaluate_grouped(self.theta)
+            else:                     # flagged Nesterov groups only take it; the others are left as their uniform learner leaves them
+                loss, grad, n_ok = loss.clone(), grad.clone(), self.n_ok.clone()
+                flag = self._true_rows
+                l2, g2 = self._second_evaluation(lambda: self._evaluate_grouped(self.theta), flag.repeat_interleave(self.demos_per_seed))
+                loss, grad = torch.where(flag, l2, loss), torch.where(flag.unsqueeze(1), g2, grad)
+                self.n_ok = torch.where(flag, self.n_ok, n_ok)
+        self._append_trace(loss, grad, None)
+        return loss, grad
+
     def step(self):
         """One outer iteration; returns (loss, grad) evaluated where the update rule needs them."""
+        if self.mode == "grouped":
+            return self._step_grouped()
         if self._stop is not None:
             return self._step_stop_rule()
         self._check_trace_room()

@@ -23,6 +23,7 @@
 //   grid_sample_kernel    calling opt_sol(t) / auxsys_sol(t)                   CPDP.py:386-390 (the interpolants at arbitrary times)
 //   waypoint_vjp_kernel   `diff_loss += r @ auxsys_sol(tau)` of a user's loss   Examples/*.py getloss_corrections
 //   normal_matrix_kernel, lm_step_kernel   no counterpart: a Levenberg-Marquardt outer update from J^T J of the waypoint residuals
+//   group_reduce_kernel   no counterpart: loss, gradient and J^T J of several demonstrations summed per seed, in a fixed order
 //
 // The same source builds for the GPU with hipcc and, with -DLFSD_EMU, for the CPU
 // SIMT emulator in tests/emu (test infrastructure; never used by the product path).
@@ -30,7 +31,8 @@
 // Sources: cpdp_common.h (switches, primitives, dense helpers), cpdp_oc.h (OC solve), cpdp_aux.h (auxiliary
 // system sweeps + loss), cpdp_opt.h (update rules), cpdp_rows.h (per-seed stop rule, row compaction / gather / scatter),
 // cpdp_spline.h (curvature fit of the cubic interpolant), cpdp_sample.h (sampling the interpolants, chain rule of a user's loss),
-// cpdp_lm.h (Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step).
+// cpdp_lm.h (Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step), cpdp_groups.h (per-group sums of several
+// demonstrations per seed).
 #pragma once
 #include "cpdp_common.h"
 #include "cpdp_oc.h"
@@ -40,3 +42,4 @@
 #include "cpdp_opt.h"
 #include "cpdp_rows.h"
 #include "cpdp_lm.h"
+#include "cpdp_groups.h"

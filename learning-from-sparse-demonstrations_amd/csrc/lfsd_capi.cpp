@@ -745,3 +745,37 @@ LFSD_API int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down,
   }
   return LFSD_EINVAL;
 }
+
+// ---- ABI 15: several demonstrations per seed -- loss, gradient and J^T J summed per group in a fixed order (cpdp_groups.h) ----
+LFSD_API int lfsd_group_reduce(int dtype, int n_groups, int group_size, int n_param, const void* loss, const void* grad,
+                               const void* H, const int* row_ok, void* loss_g, void* grad_g, void* H_g, int* n_ok, void* stream) {
+  if (n_groups <= 0 || group_size <= 0 || n_param <= 0) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  if (!loss || !grad || !loss_g || !grad_g || !n_ok) return LFSD_EINVAL;
+  if ((H == nullptr) != (H_g == nullptr)) return LFSD_EINVAL;
+  // the sizes first: the byte counts of the overlap test below must not wrap (B p^2 * 8 < 2^64 needs more than p < 2^15.5 alone)
+  if (n_param > 46340) return LFSD_EINVAL;
+  {
+    const unsigned long long per = 1ull + (unsigned long long)n_param + (H ? (unsigned long long)n_param * n_param : 0ull);
+    if (((unsigned long long)n_groups * per + 255ull) / 256ull > 0x7fffffffull) return LFSD_EINVAL;      // (the launcher's workgroup limit)
+    if ((unsigned long long)n_groups * (unsigned long long)group_size > (0xffffffffffffffffull / 8ull) / ((unsigned long long)n_param * n_param))
+      return LFSD_EINVAL;
+  }
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, G = (unsigned long long)n_groups, P = (unsigned long long)n_param;
+  const unsigned long long B = G * (unsigned long long)group_size;
+  const void* in[4] = {loss, grad, H, row_ok};
+  const unsigned long long in_bytes[4] = {B * es, B * P * es, B * P * P * es, B * sizeof(int)};
+  const void* out[4] = {loss_g, grad_g, H_g, n_ok};
+  const unsigned long long out_bytes[4] = {G * es, G * P * es, G * P * P * es, G * sizeof(int)};
+  for (int o = 0; o < 4; ++o)
+    for (int i = 0; i < 4; ++i)
+      if (out[o] && spans_overlap(out[o], out_bytes[o], in[i], in_bytes[i])) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::GroupReduceArgs<float> a{n_groups, group_size, n_param, (const float*)loss, (const float*)grad, (const float*)H, row_ok,
+                                   (float*)loss_g, (float*)grad_g, (float*)H_g, n_ok};
+    return lfsd_detail::launch_group_reduce_f32(a, stream);
+  }
+  lfsd::GroupReduceArgs<double> a{n_groups, group_size, n_param, (const double*)loss, (const double*)grad, (const double*)H, row_ok,
+                                  (double*)loss_g, (double*)grad_g, (double*)H_g, n_ok};
+  return lfsd_detail::launch_group_reduce_f64(a, stream);
+}

@@ -1,6 +1,6 @@
 // Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
 // the sampling kernels (ABI 12: cpdp_sample.h), the per-row rules (ABI 13: cpdp_opt.h) and the Levenberg-Marquardt kernels (ABI 14:
-// cpdp_lm.h).  They live
+// cpdp_lm.h) and the per-group reduction (ABI 15: cpdp_groups.h).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -115,4 +115,18 @@ template <typename T> static int launch_lm_step(const lfsd::LmStepArgs<T>& a, vo
 }
 int launch_lm_step_f32(const lfsd::LmStepArgs<float>& a, void* stream) { return launch_lm_step<float>(a, stream); }
 int launch_lm_step_f64(const lfsd::LmStepArgs<double>& a, void* stream) { return launch_lm_step<double>(a, stream); }
+// ---- ABI 15: loss, gradient and Gauss-Newton matrix of several demonstrations summed per seed (cpdp_groups.h) ----
+// one thread per (group, element), 1 + p + p^2 elements per group: n_groups and n_param are positive ints, the product stays below
+// 2^62 while n_param < 2^15.5 -- larger ones are refused with the workgroup count
+template <typename T> static int launch_group_reduce(const lfsd::GroupReduceArgs<T>& a, void* stream) {
+  if (a.n_param > 46340) return LFSD_EINVAL;
+  const long long per = 1 + (long long)a.n_param + (a.H ? (long long)a.n_param * a.n_param : 0);
+  const long long threads = (long long)a.n_groups * per;
+  const long long blocks = (threads + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::group_reduce_kernel<T>), (unsigned)blocks, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_group_reduce_f32(const lfsd::GroupReduceArgs<float>& a, void* stream) { return launch_group_reduce<float>(a, stream); }
+int launch_group_reduce_f64(const lfsd::GroupReduceArgs<double>& a, void* stream) { return launch_group_reduce<double>(a, stream); }
 }

@@ -88,4 +88,7 @@ int launch_normal_matrix_f32(const lfsd::NormalMatrixArgs<float>& a, void* strea
 int launch_normal_matrix_f64(const lfsd::NormalMatrixArgs<double>& a, void* stream);
 int launch_lm_step_f32(const lfsd::LmStepArgs<float>& a, void* stream);
 int launch_lm_step_f64(const lfsd::LmStepArgs<double>& a, void* stream);
+// per-group sums of several demonstrations per seed (ABI 15, cpdp_groups.h; the same third unit)
+int launch_group_reduce_f32(const lfsd::GroupReduceArgs<float>& a, void* stream);
+int launch_group_reduce_f64(const lfsd::GroupReduceArgs<double>& a, void* stream);
 }

@@ -106,7 +106,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_groups.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
                   "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
@@ -274,7 +274,8 @@ class ModelLibrary:
                "lfsd_aux_solve", "lfsd_aux_riccati", "lfsd_aux_forward", "lfsd_optimizer_step", "lfsd_lookahead",
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
                "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
-               "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step")
+               "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step",
+               "lfsd_group_reduce")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -314,12 +315,13 @@ class ModelLibrary:
         L.lfsd_trace_append.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_normal_matrix.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_lm_step.argtypes = [ci, ci, ci, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.lfsd_group_reduce.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 14:
+        if rc != 0 or info.abi_version != 15:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -779,6 +781,45 @@ class ModelLibrary:
                                        self._p(theta_trial), self._p(loss_t), self._p(grad_t), self._p(H_t), self._p(proj_lo),
                                        self._p(row_active), self._p(accepted), self._stream(theta))
         self._rc(rc, "lfsd_lm_step")
+
+    # ---- ABI 15: several demonstrations per seed -- the per-group sums -------------------------------------------------------------
+    def group_reduce(self, loss, grad, group_size, H=None, row_ok=None, out=None):
+        """Sums of loss [B], grad [B, p] and (optionally) H [B, p, p] over the ``group_size`` consecutive rows of every group
+        (include/lfsd_cpdp.h, ABI 15): row ``g * group_size + d`` is demonstration d of group g.  ``row_ok`` [B] int32 or None: rows
+        with 0 are left out (their values may be NaN).  Returns ``(loss_g [G], grad_g [G, p], H_g [G, p, p] or None, n_ok [G] int32)``;
+        ``out``: such a tuple to write into.  Fixed summation order (0, then the rows ascending): a group's sums are the same bits in
+        any batch.  Nothing is read back."""
+        if not isinstance(grad, torch.Tensor) or grad.dim() != 2 or grad.dtype not in _DT:
+            raise LfsdError("grad must be a [B, n_param] float32 / float64 tensor")
+        B, p = grad.shape
+        dt = grad.dtype
+        if isinstance(group_size, bool) or int(group_size) != group_size or int(group_size) <= 0:
+            raise LfsdError("group_size must be a positive integer (got %r)" % (group_size,))
+        D = int(group_size)
+        if B < 1 or p < 1 or B % D != 0:
+            raise LfsdError("a batch of %d rows is not a whole number of groups of %d" % (B, D))
+        G = B // D
+        self._check(grad, (B, p), dt, "grad")
+        self._check(loss, (B,), dt, "loss")
+        self._check(H, (B, p, p), dt, "H", optional=True)
+        self._check(row_ok, (B,), torch.int32, "row_ok", optional=True)
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=dt, device=grad.device)
+            out = (new(G), new(G, p), None if H is None else new(G, p, p), torch.empty(G, dtype=torch.int32, device=grad.device))
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise LfsdError("out is a tuple (loss_g [G], grad_g [G, p], H_g [G, p, p] or None, n_ok [G])")
+        loss_g, grad_g, H_g, n_ok = out
+        if (H is None) != (H_g is None):
+            raise LfsdError("H and out's H_g are given together or not at all")
+        self._check(loss_g, (G,), dt, "loss_g")
+        self._check(grad_g, (G, p), dt, "grad_g")
+        self._check(H_g, (G, p, p), dt, "H_g", optional=True)
+        self._check(n_ok, (G,), torch.int32, "n_ok")
+        with self._on(grad):
+            rc = self.lib.lfsd_group_reduce(_DT[dt], G, D, p, self._p(loss), self._p(grad), self._p(H), self._p(row_ok),
+                                            self._p(loss_g), self._p(grad_g), self._p(H_g), self._p(n_ok), self._stream(grad))
+        self._rc(rc, "lfsd_group_reduce")
+        return loss_g, grad_g, H_g, n_ok
 
     def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
                      eligible=None):
