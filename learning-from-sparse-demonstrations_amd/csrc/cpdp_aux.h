@@ -62,11 +62,15 @@ template <typename T> struct AuxArgsCubic : AuxArgs<T> {
 
 // LAY: which packing of the staged coefficients the kernel uses (codegen: 0 Riccati sweep, every matrix; 1 forward sweep,
 // without Hxx / Hxe) -- the node stride NCOEF and every offset behind it follow
-template <class M, int LAY = 0> struct AuxLayout {
+// NSLOT: node slots in LDS -- NNODE (one split unit), or 2 NNODE - 1 where the Riccati sweep stages the nodes of two consecutive
+// units in one pass (ric_pair_stage below)
+template <class M, int LAY = 0, int NSLOT = 5> struct AuxLayout {
   static constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NZ = NX + NP, NNODE = 5;
+  static constexpr bool PAIR = NSLOT > NNODE;
+  static_assert(NSLOT == NNODE || (LAY == 0 && NSLOT == 2 * NNODE - 1), "node slots");
   static constexpr int NCOEF = M::NCOEF_L[LAY];
   static constexpr int LDS_L = 0;
-  static constexpr int LDS_S = LDS_L + NNODE * NCOEF;
+  static constexpr int LDS_S = LDS_L + NSLOT * NCOEF;
   static constexpr int LDS_T = LDS_S + NX * NU;
   // LDS_T (transposed exchange of the Riccati right-hand side) and LDS_KN/LDS_PSI (forward sweep) share one region:
   // each kernel uses only its own
@@ -97,13 +101,21 @@ template <class M, int LAY = 0> struct AuxLayout {
   static constexpr int lds_elems_fwd() { return ((FWD_RED + 128 + 3) / 4) * 4; }
   // Riccati kernel only: one parking slot per lane for a column of Z (row i of lane l at [i*G + l]): of the unit's start value and
   // the coarse Richardson result only one has to be in registers at a time
+  // (pair staging: rows NZ words apart instead of G.  The lanes beyond the last column carry no column of Z: their words of the slot are
+  //  what pays for the four extra node slots.  They park into LDS_T instead -- words [l + i*NZ], l < G - NZ, inside the exchange
+  //  buffer -- which ric_rhs overwrites between a parking write and its read: such a lane reads back ARBITRARY words, and from the
+  //  first unit on its z[] is private garbage, not zero.  That is harmless only because nothing of an idle lane is ever consumed:
+  //  the writes to LDS_S / LDS_T are gated by lane < NX, the error reduction, the symmetrisation and the stores of Z by lane < NZ,
+  //  and its hcol / ucol point at the node's zero word.  Code that reads z[] or the reduction words of lanes >= NZ must not rely on
+  //  zeros there.)
+  template <int G> static constexpr int ric_pstride() { return PAIR ? NZ : G; }
   template <int G> static constexpr int ric_park() { return LDS_END; }
   // ... and a second one: the start value of a STEP of the step-size control inside a stiff interval (aux_riccati_kernel, "adaptive")
   // (compiled into the fp32 instantiations with lane groups of at most 16 lanes -- pendulum, robot arm, cart-pole: the small models,
   //  whose sweeps have registers to spare; the 32-lane sweeps of the quadrotor / rocket run two waves per SIMD at 252 registers, spilled
   //  60 B per lane with it (headline aux_riccati 1.50 -> 1.545 ms) and stay exactly what they were)
   template <int G> static constexpr bool ric_adaptive() { return G <= 16; }
-  template <int G> static constexpr int ric_park2() { return ric_park<G>() + NX * G; }
+  template <int G> static constexpr int ric_park2() { return ric_park<G>() + NX * ric_pstride<G>(); }
   template <int G> static constexpr int lds_elems_ric() { return ((ric_park2<G>() + (ric_adaptive<G>() ? NX * G : 0) + 3) / 4) * 4; }
 };
 
@@ -122,16 +134,34 @@ template <class M> constexpr int fwd_lanes() {
   return g;
 }
 
+// LFSD_RIC_PAIR_STAGE (cpdp_common.h): the fp32 Riccati sweep of the 32-lane models along the linear interpolant stages the nine
+// distinct coefficient nodes of two consecutive split units in one pass.  Everything else -- fp64, level 2, the step-controlled sweep
+// of the small models, the forward sweep -- stages one unit at a time.
+// ... and only where the nine slots fit: the sweep runs two waves per SIMD, eight one-wave workgroups share the 160 KB of a CU, so a
+// workgroup (64 / G trajectories) may take 20 480 B.  A model whose slice is larger with nine slots (the rocket: 12 parameters, 204
+// coefficients per node -- 20 864 B) keeps five slots and the one-unit staging, bit for bit the LFSD_RIC_PAIR_STAGE=0 kernel.
+constexpr int kRicLdsPerWorkgroup = 20480;
+template <class M, typename T, int G, int LAY, int LVL> constexpr int aux_node_slots() {
+  if constexpr (LFSD_RIC_PAIR_STAGE != 0 && sizeof(T) == 4 && G == 32 && LAY == 0 && LVL == 1)
+    return (64 / G) * AuxLayout<M, 0, 9>::template lds_elems_ric<G>() * (int)sizeof(T) <= kRicLdsPerWorkgroup ? 9 : 5;
+  else
+    return 5;
+}
+// (the node slot the unit in hand starts at: a member only where units are staged in pairs, so that every other AuxCtx is what it was)
+template <bool PAIR> struct AuxNodeSlot { int nslot = 0; };
+template <> struct AuxNodeSlot<false> {};
+
 // (the prefetch registers of the curvature rows: an empty base where a kernel has none, so that AuxCtx is what it was at level 1)
 template <typename T, int N> struct AuxCurvPf { T cpf[N]; };
 template <typename T> struct AuxCurvPf<T, 0> {};
 
 // LVL: interpolation level of the nominal trajectory (1 linear, CPDP.py:386; 2 cubic, CPDP.py:388-390)
 template <class M, typename T, int G, int LAY, int LVL = 1> struct AuxCtx
-    : AuxCurvPf<T, (sizeof(T) == 4 && LVL == 2 && (LAY == 1 || G <= 16)) ? (2 * M::NX + M::NU + G - 1) / G : 0> {
+    : AuxCurvPf<T, (sizeof(T) == 4 && LVL == 2 && (LAY == 1 || G <= 16)) ? (2 * M::NX + M::NU + G - 1) / G : 0>,
+      AuxNodeSlot<(aux_node_slots<M, T, G, LAY, LVL>() > 5)> {
   static_assert(LVL == 1 || LVL == 2, "interpolation level");
   static constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NC = M::NC, NZ = NX + NP;
-  using Lay = AuxLayout<M, LAY>;
+  using Lay = AuxLayout<M, LAY, aux_node_slots<M, T, G, LAY, LVL>()>;
   static constexpr int H = G / 2;      // forward sweep: first lane of the coarse Richardson chain
   int lane;
   int xcol;                  // forward sweep: column of X = dx/dtheta (and of W) this lane carries (fine chain: lanes < NP,
@@ -228,9 +258,15 @@ template <class M, typename T, int G, int LAY, int LVL = 1> struct AuxCtx
   }
   // Lane `node` (< 5) evaluates the packed PMP coefficients at its own time node s (fraction of the
   // interval) on the reference's interpolant of (x,u,lambda) (CPDP.py:320-323; linear, or at level 2 cubic) and stages them in LDS.
-  LFSD_DEV void stage_nodes(T s_first, T s_step) {
-    if (lane < Lay::NNODE) {
-      const T s = s_first + s_step * T(lane);
+  // Pair staging (`nn` = 9): lanes 5-8 take nodes 1-4 of the NEXT unit, whose first node sits at s_next; node 4 of this unit is node 0
+  // of the next and is stored once -- the caller pairs two units only where both expressions give the same fraction (pair_ok).  Every
+  // lane forms its fraction as the one-unit pass of ITS unit does, first node + s_step * index: the staged coefficients are bit-equal.
+  LFSD_DEV void stage_nodes(T s_first, T s_step, T s_next = T(0), int nn = Lay::NNODE) {
+    if (lane < (Lay::PAIR ? nn : Lay::NNODE)) {
+      T sf = s_first;
+      int li = lane;
+      if constexpr (Lay::PAIR) { if (lane >= Lay::NNODE) { sf = s_next; li = lane - (Lay::NNODE - 1); } }
+      const T s = sf + s_step * T(li);
       T x[NX], u[NU], l[NX];
 #pragma unroll
       for (int i = 0; i < NX; ++i) { x[i] = xa_[i] + s * (xb_[i] - xa_[i]); l[i] = la_[i] + s * (lb_[i] - la_[i]); }
@@ -257,7 +293,22 @@ template <class M, typename T, int G, int LAY, int LVL = 1> struct AuxCtx
     }
     LFSD_WAVE_SYNC();
   }
-  LFSD_DEV const T* node(int i) const { return lds + Lay::LDS_L + i * Lay::NCOEF; }
+  LFSD_DEV static bool pair_ok(T s_first, T s_step, T s_next) { return s_first + s_step * T(Lay::NNODE - 1) == s_next; }
+  // Pair staging: the unit in hand reads its five nodes from slot `nslot` on (0 or 4); node() and the column pointers move with it
+  LFSD_DEV void node_base(int slot) {
+    if constexpr (Lay::PAIR) {
+      const int d = (slot - this->nslot) * Lay::NCOEF;
+      this->nslot = slot;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) hcol[i] += d;
+#pragma unroll
+      for (int a = 0; a < NU; ++a) ucol[a] += d;
+    }
+  }
+  LFSD_DEV const T* node(int i) const {
+    if constexpr (Lay::PAIR) return lds + Lay::LDS_L + (this->nslot + i) * Lay::NCOEF;
+    else return lds + Lay::LDS_L + i * Lay::NCOEF;
+  }
   // component i of x(t_k + s dgrid) on the interpolant (the waypoint loss: opt_sol(tau), lib/QuadAlgorithm.py:625)
   LFSD_DEV T state_at(int i, T s) const {
     T v = xa_[i] + s * (xb_[i] - xa_[i]);
@@ -651,7 +702,7 @@ template <class M, typename T, int G, int LAY, int LVL = 1> struct AuxCtx
 template <class M, typename T, int G, int LAY, int LVL> LFSD_DEV void aux_setup(AuxCtx<M, T, G, LAY, LVL>& s, const AuxArgs<T>& a, long long traj,
                                                             T* lds_all, int lds_stride) {
   constexpr int NX = M::NX, NP = M::NP, NC = M::NC;
-  using Lay = AuxLayout<M, LAY>;
+  using Lay = typename AuxCtx<M, T, G, LAY, LVL>::Lay;
   const int gib = threadIdx.x / G;
   s.lane = threadIdx.x % G;
   s.coarse = (LAY == 1) && (s.lane >= G / 2);

@@ -11,10 +11,18 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) LFSD_AUX_RICCATI
   constexpr int LVL = LFSD_AUX_LVL;
   if (blockDim.x != 64) return;                   // one wavefront per workgroup: see the note on barriers above
   using Ctx = AuxCtx<M, T, G, 0, LVL>;
-  using Lay = AuxLayout<M>;
+  using Lay = typename Ctx::Lay;
   constexpr int NX = M::NX, NP = M::NP, NZ = NX + NP;
   constexpr int GPB = 64 / G;
   static_assert(64 % G == 0 && G >= NZ && G >= Lay::NNODE, "lane group must hold one column of [P W] per lane");
+  // pair staging (LFSD_RIC_PAIR_STAGE, cpdp_aux.h): nine staging lanes; the parking slot holds the NZ columns only, and the lanes
+  // beyond them park into the exchange buffer LDS_T and read back whatever ric_rhs left there: their z[] is private and ARBITRARY (not
+  // zero), and nothing below may consume it (AuxLayout::ric_pstride)
+  constexpr bool PAIR = Lay::PAIR;
+  constexpr int PS = Lay::template ric_pstride<G>();
+  static_assert(!PAIR || (G >= 2 * Lay::NNODE - 1 && !Lay::template ric_adaptive<G>() && (G - NZ) + (NX - 1) * NZ <= Lay::LDS_TSZ &&
+                          GPB * Lay::template lds_elems_ric<G>() * (int)sizeof(T) <= kRicLdsPerWorkgroup),
+                "pair staging: nine staging lanes, uniform units only, idle lanes park inside LDS_T, eight workgroups per CU");
   constexpr int LDS_SLICE = Lay::template lds_elems_ric<G>() + (LVL == 2 ? Lay::CURV : 0);
   __shared__ T lds_all[GPB * LDS_SLICE];
   poison_lds(lds_all, GPB * LDS_SLICE);
@@ -70,7 +78,15 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) LFSD_AUX_RICCATI
     // are staged for the first unit of the expected unit count at once: node 0 sits at the interval end either way, and
     // when the stiffness estimate confirms the count the first unit need not stage again
     const int units_guess = units_hint;
-    s.stage_nodes(T(1), T(-1) / T(4 * units_guess));
+    int ahead = 1;      // units whose nodes the last staging pass has put in place (pair staging: 2 after a nine-node pass)
+    if constexpr (PAIR) {
+      const T st0 = T(-1) / T(4 * units_guess), s_nx = T(1) - T(1) / T(units_guess);
+      if (units_guess >= 2 && Ctx::pair_ok(T(1), st0, s_nx)) ahead = 2;
+      s.node_base(0);
+      s.stage_nodes(T(1), st0, s_nx, ahead == 2 ? 2 * Lay::NNODE - 1 : Lay::NNODE);
+    } else {
+      s.stage_nodes(T(1), T(-1) / T(4 * units_guess));
+    }
     const int refine_k = (budget > 0 && n_units >= budget) ? 1 : a.max_refine;      // budget spent: no refinement
     int units = s.units_for(s.stiff_rate(z, s.node(0)), Sa, a.rate_max, refine_k);
     // error-driven refinement stops at max_refine x the minimum units -- and as soon as a doubling fails to halve the
@@ -166,22 +182,36 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) LFSD_AUX_RICCATI
       const T hc = s.dgrid / T(units);
       const T ds = T(1) / T(4 * units);
       T err_l = T(0), scl_l = T(0);
+      if (!staged) ahead = 0;      // (a redo, or a unit count other than the guess: staged anew from the first unit on)
       for (int unit = 0; unit < units; ++unit) {
         const T s_hi = T(1) - T(unit) / T(units);
-        if (!(staged && unit == 0)) s.stage_nodes(s_hi, -ds);      // node i sits at fraction s_hi - i/(4 units)
+        if constexpr (PAIR) {
+          // two units per staging pass while two are left (and their shared node is one fraction); the second of a pair reads slots 4-8
+          if (ahead == 0) {
+            const T s_nx = T(1) - T(unit + 1) / T(units);
+            ahead = (unit + 1 < units && Ctx::pair_ok(s_hi, -ds, s_nx)) ? 2 : 1;
+            s.node_base(0);
+            s.stage_nodes(s_hi, -ds, s_nx, ahead == 2 ? 2 * Lay::NNODE - 1 : Lay::NNODE);
+          } else if (unit > 0) {
+            s.node_base(Lay::NNODE - 1);
+          }
+          --ahead;
+        } else {
+          if (!(staged && unit == 0)) s.stage_nodes(s_hi, -ds);      // node i sits at fraction s_hi - i/(4 units)
+        }
         staged = false;
         // coarse chain in place, then the fine chain in place from the parked start value (the barriers inside the chains
         // keep the compiler from carrying the parked column in registers)
-        T* zpark = s.lds + Lay::template ric_park<G>();
+        T* zpark = s.lds + ((PAIR && lane >= NZ) ? Lay::LDS_T + lane - NZ : Lay::template ric_park<G>() + lane);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) zpark[i * G + lane] = z[i];
+        for (int i = 0; i < NX; ++i) zpark[i * PS] = z[i];
         s.ric_strang(z, 0, 2, 4, hc);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) { const T z0 = zpark[i * G + lane]; zpark[i * G + lane] = z[i]; z[i] = z0; }
+        for (int i = 0; i < NX; ++i) { const T z0 = zpark[i * PS]; zpark[i * PS] = z[i]; z[i] = z0; }
         s.ric_strang2(z, hc);
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-          const T zc = zpark[i * G + lane];
+          const T zc = zpark[i * PS];
           err_l = t_max(err_l, t_abs(z[i] - zc));
           z[i] = (T(4) * z[i] - zc) * (T(1) / T(3));     // Richardson (Strang is O(h^2), symmetric); constant reciprocal: no division
           scl_l = t_max(scl_l, t_abs(z[i]));

@@ -56,6 +56,11 @@
 #ifndef LFSD_BW_SMALL
 #define LFSD_BW_SMALL 1
 #endif
+// fp32 Riccati sweep of the 32-lane models (cpdp_aux.h, aux_node_slots): the coefficient nodes of two consecutive split units are
+// staged in one pass on nine lanes (1), or every unit stages its own five (0).  The results are bit for bit the same.
+#ifndef LFSD_RIC_PAIR_STAGE
+#define LFSD_RIC_PAIR_STAGE 1
+#endif
 
 // ---- scheduling fences and LDS hand-overs -------------------------------------------------------------------------------------
 // LFSD_ROW_FENCE / LFSD_SCHED_FENCE64(T): the instruction scheduler moves nothing across this point (bounds the live ranges of

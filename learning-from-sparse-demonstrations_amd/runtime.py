@@ -240,7 +240,9 @@ def build_variant_library(spec, tag, flags):
 PLAIN_SCHEDULE = ("-DLFSD_LEAN_TC=1", "-DLFSD_COARSE_START=0", "-DLFSD_COARSE_TIME=1", "-DLFSD_MS=0")
 GPU_TIER_VARIANTS = (("quadrotor", 50, "nocoarse", ("-DLFSD_COARSE_START=0",)),
                      ("quadrotor", 50, "plain", PLAIN_SCHEDULE), ("cartpole", 40, "plain", PLAIN_SCHEDULE),
-                     ("rocket", 40, "plain", PLAIN_SCHEDULE), ("robotarm", 50, "plain", PLAIN_SCHEDULE))
+                     ("rocket", 40, "plain", PLAIN_SCHEDULE), ("robotarm", 50, "plain", PLAIN_SCHEDULE),
+                     # the Riccati sweep with one staging pass per split unit (tests/test_riccati_pair_stage_gpu.py)
+                     ("quadrotor", 50, "ricpair0", ("-DLFSD_RIC_PAIR_STAGE=0",)))
 
 
 def build_gpu_tier_variants(verbose=False):
