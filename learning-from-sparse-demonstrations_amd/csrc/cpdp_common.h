@@ -4,6 +4,7 @@
 
 
 #include <type_traits>
+#include <utility>
 #if defined(LFSD_EMU)
 #include "simt_emu.h"
 #define LFSD_LAMBDA_INLINE
@@ -60,6 +61,12 @@
 // staged in one pass on nine lanes (1), or every unit stages its own five (0).  The results are bit for bit the same.
 #ifndef LFSD_RIC_PAIR_STAGE
 #define LFSD_RIC_PAIR_STAGE 1
+#endif
+// lean fp32 OC kernel of the 32-lane models (cpdp_oc.h, OcSolver::backward_sc / costate_sweep_sc): the per-stage hand-overs inside a
+// trajectory's 16-lane group -- Q_uu and Q_u, the gains, Q_ux, V_x and the costate -- are row broadcasts in registers (row_bcast
+// below, 1), or go through LDS (0).  Data movement only: the results are bit for bit the same.
+#ifndef LFSD_OC_DPP_XCHG
+#define LFSD_OC_DPP_XCHG 1
 #endif
 
 // ---- scheduling fences and LDS hand-overs -------------------------------------------------------------------------------------
@@ -701,6 +708,65 @@ template <int Q, typename T> LFSD_DEV T sub_bcast(T v, int k) {
   else return k == 0 ? dpp_mov<0x00>(v) : (k == 1 ? dpp_mov<0x55>(v) : (k == 2 ? dpp_mov<0xAA>(v) : dpp_mov<0xFF>(v)));
 }
 #endif
+// row_bcast(v, k): v of lane k (0..15) of the caller's 16-lane row -- lanes 16r .. 16r+15 of the wavefront, the lane group of the lean
+// OC kernels' backward sweep -- in every lane of it.  On the GPU one DPP move (row_newbcast:k), which the compiler folds into the
+// instruction that consumes it where that instruction takes a DPP operand (v_fmac_f32, v_max_f32, ...): no LDS trip and no wait; k
+// must be a constant after unrolling (the switch below folds to one move then; a k that is not would compile to sixteen).  bound_ctrl is
+// set, so a SOURCE lane that EXEC has switched off would deliver 0 instead of its value.  A source lane always lies in the reader's
+// own row, so what the callers have to keep is that control flow is uniform WITHIN a row: a row is a lane group, and a group takes
+// every branch as one (padded and finished groups ride along; groups may part from each other).  The sweeps in fact run whole
+// wavefronts through one control flow, which is what the emulator's exchange buffer needs.
+// row_max(v, first, n): max of t_max-folded v over lanes first .. first+n-1 of the row, from T(0), in lane order, on every lane.
+constexpr bool row_xchg_ok(int lanes) { return lanes == 16; }      // a lane group that is exactly one DPP row
+#if defined(LFSD_EMU)
+template <typename T> inline T row_bcast(T v, int k) {
+  static T sb[EMU_MAXT];
+  const int l = threadIdx.x;
+  sb[l] = v;
+  __syncthreads();
+  const T r = sb[(l & ~15) | k];
+  __syncthreads();
+  return r;
+}
+#else
+LFSD_DEV float row_bcast(float v, int k) {
+  switch (k) {
+    case 0: return dpp_mov<0x150>(v);   case 1: return dpp_mov<0x151>(v);   case 2: return dpp_mov<0x152>(v);   case 3: return dpp_mov<0x153>(v);
+    case 4: return dpp_mov<0x154>(v);   case 5: return dpp_mov<0x155>(v);   case 6: return dpp_mov<0x156>(v);   case 7: return dpp_mov<0x157>(v);
+    case 8: return dpp_mov<0x158>(v);   case 9: return dpp_mov<0x159>(v);   case 10: return dpp_mov<0x15A>(v);  case 11: return dpp_mov<0x15B>(v);
+    case 12: return dpp_mov<0x15C>(v);  case 13: return dpp_mov<0x15D>(v);  case 14: return dpp_mov<0x15E>(v);  default: return dpp_mov<0x15F>(v);
+  }
+}
+#endif
+// fmac2_row_bcast<K>(acc, a, wa, b, wb): acc += row_bcast(a, K) * wa; acc += row_bcast(b, K) * wb -- in this order, each ONE
+// v_fmac_f32 with the broadcast as its DPP operand (the fused multiply-adds the compiler contracts the two statements to, so the
+// bits are those of the LDS-fed statements; it does not fold a DPP move into them by itself -- 104 moves per stage of the
+// backward sweep).  The compiler's hazard recognizer does not look into the statement: the DPP operands a, b must have been
+// written at least two wait states earlier, and a vector write of EXEC five.  The callers pass values that a dependent chain
+// separates from this point and start a run with dpp_settle(), but neither binds the register allocator or the scheduler (a copy
+// back from an AGPR may land anywhere): what GUARANTEES the distances is the scan of every build's assembly, isa_check.py's
+// find_dpp_hazards, which rejects a build that has a writer too close to any DPP instruction (runtime.py: _checked_build).
+#if defined(LFSD_EMU)
+inline void dpp_settle() {}
+template <int K> inline void fmac2_row_bcast(float& acc, float a, float wa, float b, float wb) {
+  acc += row_bcast(a, K) * wa;
+  acc += row_bcast(b, K) * wb;
+}
+#else
+LFSD_DEV void dpp_settle() { asm volatile("s_nop 4"); }
+template <int K> LFSD_DEV void fmac2_row_bcast(float& acc, float a, float wa, float b, float wb) {
+  static_assert(K >= 0 && K < 16, "lane of the row");
+  asm volatile("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%5 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+               "v_fmac_f32_dpp %0, %3, %4 row_newbcast:%5 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+               : "+v"(acc) : "v"(a), "v"(wa), "v"(b), "v"(wb), "n"(K));
+}
+#endif
+template <typename T> LFSD_DEV T row_max(T v, int first, int n) {
+  T r = T(0);
+#pragma unroll
+  for (int a = 0; a < n; ++a) r = t_max(r, row_bcast(v, first + a));
+  return r;
+}
 // smallest sub-group that holds one row per lane of an n x n matrix (n <= 4)
 template <int n> constexpr int sub_lanes() { return n <= 1 ? 1 : (n == 2 ? 2 : 4); }
 // W = A B, row a of each matrix in lane a of the sub-group (lanes a >= n carry zeros); same summation order as matmul<n>

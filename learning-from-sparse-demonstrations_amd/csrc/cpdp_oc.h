@@ -1487,6 +1487,21 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
   // other lanes publish in LDS.  The stage Hessian of a constant state couples to nothing outside Z (codegen checks), so
   // one ham_hess_mul with BOTH one-hots set returns the control column's entries and the constant state's side by side.
   static constexpr int ZC = Lay::ZC, LIVE = Lay::LIVE, LX = NX - Lay::ZC, MS = Lay::MS_ELEMS, LIVEP = Lay::LIVEP;
+  // LFSD_OC_DPP_XCHG (cpdp_common.h): the fp32 structural sweeps hand Q_uu, Q_u, the gains, Q_ux, V_x and the costate from lane to lane
+  // of the group by row broadcasts (the group is one DPP row) instead of through LDS.  sc_lane(i): the lane whose V-role is state i.
+  static constexpr bool XD = (LFSD_OC_DPP_XCHG != 0) && sizeof(T) == 4 && row_xchg_ok(G);
+  static constexpr int sc_lane(int i) { return i < ZC ? LX + i : i - ZC; }
+  // vcol[i] += sum_a K[i][a] t1[a] + Q_ux[i][a] Kj[a], the two terms alternating as in the LDS-fed loop of backward_sc; rows i of K and
+  // Q_ux are Kj / Quxj of lane sc_lane(i), taken as the DPP operand of the FMAs (fmac2_row_bcast, cpdp_common.h: Kj and Quxj were
+  // written before the dependent chain that produced t1)
+  template <int I> LFSD_DEV void sc_vrow(T& sacc, const T* Kj, const T* t1, const T* Quxj) const {
+#pragma unroll
+    for (int a = 0; a < NU; ++a) fmac2_row_bcast<sc_lane(I)>(sacc, Kj[a], t1[a], Quxj[a], Kj[a]);
+  }
+  template <int... I> LFSD_DEV void sc_vrows(T* vcol, const T* Kj, const T* t1, const T* Quxj, std::integer_sequence<int, I...>) const {
+    dpp_settle();
+    (sc_vrow<I>(vcol[I], Kj, t1, Quxj), ...);
+  }
   LFSD_DEV T rollout_sens_sc(int cur, int nxt, T alpha, bool gains) {
     using V = pk2<T>;
     T x[NX], u[NU], J = T(0);
@@ -1629,6 +1644,10 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       }
     }
     __syncthreads();
+    // XD: V_x and the costate of this lane's OWN V-role state, carried from stage to stage (what ldsVx[zi] / ldsLam[zi] hold for the
+    // lanes of the constant states, the only ones that use them)
+    T Vx_own = T(0), lam_own = T(0);
+    if constexpr (XD) { Vx_own = ldsVx[sv]; lam_own = ldsLam[sv]; }
     T m[NX], mq = T(0), qzl = T(0);
     sc_load_stage(cur, N - 1, m, mq, qzl, xk, uk);
     for (int k = N - 1; k >= 0; --k) {
@@ -1727,12 +1746,14 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       T gzv[LIVE];                                 // row zi of Y, every live column: issued back to back for ALL lanes (pin)
 #pragma unroll
       for (int j = 0; j < LIVE; ++j) gzv[j] = ldsYZ[j * ZC + zi];
-      // (Vx and the costate of the constant state: from their LDS images -- still the incoming values here; a per-lane
-      //  select over the register copies makes the compiler park both arrays in scratch)
-      T Vx_z = ldsVx[zi], lam_z = ldsLam[zi];
+      // (Vx and the costate of the constant state: the values this lane carries for its own V-role state from the stage before
+      //  -- still the incoming ones here.  The LDS-path build reads them from their LDS images instead: a per-lane select over
+      //  the register copies of the whole vectors makes the compiler park both arrays in scratch)
+      T Vx_z, lam_z;
+      if constexpr (XD) { Vx_z = Vx_own; lam_z = lam_own; } else { Vx_z = ldsVx[zi]; lam_z = ldsLam[zi]; }
 #pragma unroll
       for (int j = 0; j < LIVE; ++j) pin(gzv[j]);
-      pin(Vx_z); pin(lam_z);
+      if constexpr (!XD) { pin(Vx_z); pin(lam_z); }
 #pragma unroll
       for (int j = 0; j < LX; ++j)                 // Q(live state ZC + j, constant state zi) = Y(zi, that column)
         Qcol[ZC + j] = st_zc ? gzv[j] : acc[j] + dgrid * hx[ZC + j];
@@ -1742,24 +1763,41 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       for (int a = 0; a < NU; ++a) Quxj[a] = st_zc ? gzv[LX + a] : mu_rows[a];
       const T Qg_v = st_zc ? qzl + Vx_z : Qg;
       const T gl_v = st_zc ? qzl + lam_z : gl;
-      if (has_v) {
-#pragma unroll
-        for (int a = 0; a < NU; ++a) ldsQux[sv * NU + a] = Quxj[a];
-      }
-      if (ctl) {
-        const int b = lane - LX;
-#pragma unroll
-        for (int a = 0; a < NU; ++a) ldsQuu[b * NU + a] = mu_rows[a];
-        ldsQu[b] = Qg;
-        gl_max = t_max(gl_max, t_abs(gl));
-      }
-      LFSD_STAGE_SYNC();
       T Quu0[NU * NU], Lc[NU * NU], Qu[NU], kff[NU], Kj[NU], t1[NU];
+      if constexpr (XD) {
+        if (ctl) gl_max = t_max(gl_max, t_abs(gl));
+        // row b of Q_uu and entry b of Q_u live on control lane LX + b: NU * NU + NU broadcasts, no LDS and no wait
+        T Qr[NU * NU];
 #pragma unroll
-      for (int a = 0; a < NU; ++a) {
-        Qu[a] = ldsQu[a];
+        for (int b = 0; b < NU; ++b) {
 #pragma unroll
-        for (int b = 0; b < NU; ++b) Quu0[a * NU + b] = T(0.5) * (ldsQuu[b * NU + a] + ldsQuu[a * NU + b]);
+          for (int a = 0; a < NU; ++a) Qr[b * NU + a] = row_bcast(mu_rows[a], LX + b);
+          Qu[b] = row_bcast(Qg, LX + b);
+        }
+#pragma unroll
+        for (int a = 0; a < NU; ++a) {
+#pragma unroll
+          for (int b = 0; b < NU; ++b) Quu0[a * NU + b] = T(0.5) * (Qr[b * NU + a] + Qr[a * NU + b]);
+        }
+      } else {
+        if (has_v) {
+#pragma unroll
+          for (int a = 0; a < NU; ++a) ldsQux[sv * NU + a] = Quxj[a];
+        }
+        if (ctl) {
+          const int b = lane - LX;
+#pragma unroll
+          for (int a = 0; a < NU; ++a) ldsQuu[b * NU + a] = mu_rows[a];
+          ldsQu[b] = Qg;
+          gl_max = t_max(gl_max, t_abs(gl));
+        }
+        LFSD_STAGE_SYNC();
+#pragma unroll
+        for (int a = 0; a < NU; ++a) {
+          Qu[a] = ldsQu[a];
+#pragma unroll
+          for (int b = 0; b < NU; ++b) Quu0[a * NU + b] = T(0.5) * (ldsQuu[b * NU + a] + ldsQuu[a * NU + b]);
+        }
       }
 #pragma unroll
       for (int i = 0; i < NU * NU; ++i) Lc[i] = Quu0[i];
@@ -1782,10 +1820,12 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
       for (int a = 0; a < NU; ++a) { Vxj += Kj[a] * (qk[a] + Qu[a]); Vxj += Quxj[a] * kff[a]; }
       if (has_v) {
+        if constexpr (!XD) {
 #pragma unroll
-        for (int a = 0; a < NU; ++a) ldsK[sv * NU + a] = Kj[a];
-        ldsVx[sv] = Vxj;
-        ldsLam[sv] = gl_v;
+          for (int a = 0; a < NU; ++a) ldsK[sv * NU + a] = Kj[a];
+          ldsVx[sv] = Vxj;
+          ldsLam[sv] = gl_v;
+        }
         if (live) {
           T* Kout = Kws + ((long long)k * NX + sv) * NU;
 #pragma unroll
@@ -1796,17 +1836,26 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
         for (int a = 0; a < NU; ++a) kws[k * NU + a] = kff[a];
       }
-      LFSD_STAGE_SYNC();
+      if constexpr (!XD) LFSD_STAGE_SYNC();
       matvec<NU>(Quu0, Kj, t1);
 #pragma unroll
       for (int a = 0; a < NU; ++a) t1[a] += Quxj[a];
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         T sacc = Qcol[i];
+        if constexpr (XD) {
+          // V_x(i) and the costate of state i come from the lane of that state (rows i of K and Q_ux: sc_vrows below)
+          Vx[i] = row_bcast(Vxj, sc_lane(i)); lam[i] = row_bcast(gl_v, sc_lane(i));
+        } else {
 #pragma unroll
-        for (int a = 0; a < NU; ++a) { sacc += ldsK[i * NU + a] * t1[a]; sacc += ldsQux[i * NU + a] * Kj[a]; }      // (two FMAs; one statement compiles to mul + fma + add)
+          for (int a = 0; a < NU; ++a) { sacc += ldsK[i * NU + a] * t1[a]; sacc += ldsQux[i * NU + a] * Kj[a]; }      // (two FMAs; one statement compiles to mul + fma + add)
+          if (VXR) { Vx[i] = ldsVx[i]; lam[i] = ldsLam[i]; }
+        }
         vcol[i] = sacc;
-        if (VXR) { Vx[i] = ldsVx[i]; lam[i] = ldsLam[i]; }
+      }
+      if constexpr (XD) {
+        sc_vrows(vcol, Kj, t1, Quxj, std::make_integer_sequence<int, NX>());
+        Vx_own = Vxj; lam_own = gl_v;
       }
       if (lane == 0 && live) {
 #pragma unroll
@@ -1834,12 +1883,16 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
       }
       if (k > 0) sc_load_stage(cur, k - 1, m, mq, qzl, xk, uk);
     }
-    ldsRed[lane] = gl_max;
-    __syncthreads();
-    gnorm = T(0);
+    if constexpr (XD) {
+      gnorm = row_max(gl_max, LX, NU);
+    } else {
+      ldsRed[lane] = gl_max;
+      __syncthreads();
+      gnorm = T(0);
 #pragma unroll
-    for (int a = 0; a < NU; ++a) gnorm = t_max(gnorm, ldsRed[LX + a]);
-    __syncthreads();
+      for (int a = 0; a < NU; ++a) gnorm = t_max(gnorm, ldsRed[LX + a]);
+      __syncthreads();
+    }
     if (!t_finite(gnorm) || !t_finite(dV1) || !t_finite(dV2)) ok = false;
     return ok;
   }
@@ -1866,6 +1919,8 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
     }
     __syncthreads();
     T gl_max = T(0);
+    T lam_own = T(0);                              // XD: the costate of this lane's own V-role state (backward_sc)
+    if constexpr (XD) lam_own = ldsLam[sv];
     T m[NX], mq = T(0), qzl = T(0), mN[NX], mqN = T(0), qzN = T(0);
     sc_load_stage(cur, N - 1, m, mq, qzl, xk, uk);
     for (int k = N - 1; k >= 0; --k) {
@@ -1874,29 +1929,39 @@ template <class M, typename T, int G, bool EXACT, bool BND = false> struct OcSol
 #pragma unroll
       for (int i = 0; i < NX; ++i) gl += m[i] * lam[i];
       if (ctl) gl_max = t_max(gl_max, t_abs(gl));
-      T lam_z = ldsLam[zi];                        // (incoming costate of the constant state, from its LDS image)
-      pin(lam_z);
-      const T glz = qzl + lam_z;
-      __syncthreads();
-      if (has_v) ldsLam[sv] = st_zc ? glz : gl;
-      __syncthreads();
+      if constexpr (XD) {
+        lam_own = st_zc ? qzl + lam_own : gl;
 #pragma unroll
-      for (int i = 0; i < NX; ++i) lam[i] = ldsLam[i];
+        for (int i = 0; i < NX; ++i) lam[i] = row_bcast(lam_own, sc_lane(i));
+      } else {
+        T lam_z = ldsLam[zi];                        // (incoming costate of the constant state, from its LDS image)
+        pin(lam_z);
+        const T glz = qzl + lam_z;
+        __syncthreads();
+        if (has_v) ldsLam[sv] = st_zc ? glz : gl;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NX; ++i) lam[i] = ldsLam[i];
+      }
       if (lane == 0 && live) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) lam_out[k * NX + i] = lam[i];
       }
-      __syncthreads();
+      if constexpr (!XD) __syncthreads();
 #pragma unroll
       for (int i = 0; i < NX; ++i) m[i] = mN[i];
       mq = mqN; qzl = qzN;
     }
-    ldsRed[lane] = gl_max;
-    __syncthreads();
-    gnorm = T(0);
+    if constexpr (XD) {
+      gnorm = row_max(gl_max, LX, NU);
+    } else {
+      ldsRed[lane] = gl_max;
+      __syncthreads();
+      gnorm = T(0);
 #pragma unroll
-    for (int a = 0; a < NU; ++a) gnorm = t_max(gnorm, ldsRed[LX + a]);
-    __syncthreads();
+      for (int a = 0; a < NU; ++a) gnorm = t_max(gnorm, ldsRed[LX + a]);
+      __syncthreads();
+    }
   }
 
   // Lane l tries step length 2^-l (all candidate roll-outs run concurrently in the group).

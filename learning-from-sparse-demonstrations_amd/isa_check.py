@@ -145,8 +145,144 @@ def find_exec_hazards(asm_text):
     return hazards
 
 
+# ---- wait states in front of DPP instructions -------------------------------------------------------------------------------------
+# A DPP instruction reads its src0 from OTHER lanes, early in the pipeline.  gfx9 / CDNA wants
+#   * 2 wait states between a vector instruction that writes the VGPR and the DPP instruction that reads it as src0,
+#   * 5 wait states between a vector instruction that writes EXEC (v_cmpx*, v_readlane / v_readfirstlane into exec) and ANY DPP instruction,
+# and, as for every vector instruction, a distance between a matrix instruction and a reader of its result (by the number of passes)
+# and 1 wait state behind a transcendental one.  The compiler's hazard recognizer inserts s_nop for the DPP instructions it emits
+# itself; it does NOT look into an `asm` statement (cpdp_common.h: fmac2_row_bcast writes v_fmac_f32_dpp by hand), and which
+# instructions the register allocator and the scheduler put in front of the statement -- a v_accvgpr_read_b32 that brings the operand
+# back from an AGPR, say -- is nothing the source controls.  A DPP instruction that comes too early reads the register's PREVIOUS
+# value: wrong numbers, no fault.  So every `*_dpp` instruction of every build is examined, the compiler's own included (they must
+# come out clean, which checks the scan), along every path that leads to it: a label's predecessors are the instruction in front
+# of it and every branch to it.  An instruction is one wait state, `s_nop N` is N + 1; a taken branch counts as one like any other.
+_DPP = re.compile(r"^(v_\w+_dpp)\s+(.*?)\s+(?:quad_perm:|row_\w+|wave_\w+|bank_mask:|bound_ctrl:|fi:)")
+_LABEL = re.compile(r"^(\.L[\w$.]+):")
+_BRANCH = re.compile(r"^s_c?branch\w*\s+(\.L[\w$.]+)")
+_END = ("s_branch", "s_endpgm", "s_setpc_b64")      # nothing falls through these
+_TRANS = ("v_exp_", "v_log_", "v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_")
+_NOP = re.compile(r"^s_nop\s+(\d+)")
+_MFMA_SHAPE = re.compile(r"_(\d+)x\d+x?\d*")
+DPP_SRC0_WAIT, DPP_EXEC_WAIT, TRANS_WAIT = 2, 5, 1
+
+
+def _mfma_wait(op):
+    """wait states between a matrix instruction and a vector read of its result: 2 / 8 / 16 passes -> 5 / 11 / 19 (the larger figure
+    where one tile edge comes with two pass counts)."""
+    m = _MFMA_SHAPE.search(op)
+    edge = int(m.group(1)) if m else 32
+    return 5 if edge <= 4 else (11 if edge <= 16 else 19)
+
+
+def _vector_writes(instr):
+    """VGPRs a vector instruction writes (compares write SGPRs / EXEC; the swaps write both operands)."""
+    parts = instr.split(";")[0].split(None, 1)
+    if len(parts) < 2 or not parts[0].startswith("v_") or parts[0].startswith("v_cmp"):
+        return set()
+    ops = parts[1].split(",")
+    if parts[0].startswith("v_swap") or (parts[0].startswith("v_permlane") and "swap" in parts[0]):
+        return _regs(",".join(ops[:2]))
+    return _regs(ops[0])
+
+
+def _writes_exec_vector(instr):
+    op = instr.split(None, 1)[0]
+    return op.startswith("v_cmpx") or (op.startswith(("v_readlane", "v_readfirstlane")) and re.match(r"^\S+\s+exec", instr) is not None)
+
+
+def find_dpp_hazards(asm_text):
+    """-> list of {"function", "block", "line", "kind": "dpp-src0"|"dpp-exec"|"dpp-mfma"|"dpp-trans", "instr", "writer", "writer_line"}: DPP
+    instructions with too few wait states behind a writer (see above)."""
+    ins, line_of, func_of, labelled, first = [], [], [], [], set()      # instructions; per instruction: line, function, labels in front
+    branches = {}                                                       # label -> instructions that branch to it
+    func, pending, entry = None, [], True
+    for i, ln in enumerate(asm_text.split("\n")):
+        t = ln.strip()
+        if not t or t.startswith(";"):
+            continue
+        m = _FUNC.match(ln)
+        if m and not ln.startswith(".L"):
+            func, pending, entry = m.group(1), [], True
+            continue
+        m = _LABEL.match(t)
+        if m:
+            pending.append(m.group(1))
+            continue
+        if t.startswith(".") or t.endswith(":"):      # directives
+            continue
+        t = t.split(";")[0].strip()
+        if not t:
+            continue
+        k = len(ins)
+        ins.append(t)
+        line_of.append(i + 1)
+        func_of.append(func)
+        labelled.append(pending)
+        if entry:
+            first.add(k)
+        pending, entry = [], False
+        m = _BRANCH.match(t)
+        if m:
+            branches.setdefault(m.group(1), []).append(k)
+
+    def preds(p):
+        out = []
+        if p not in first and p > 0 and not ins[p - 1].startswith(_END):
+            out.append(p - 1)
+        for lab in labelled[p]:
+            out.extend(branches.get(lab, ()))
+        return out
+
+    def writer_within(d, window, is_writer):
+        stack, seen = [(d, window)], {}
+        while stack:
+            p, w = stack.pop()
+            for q in preds(p):
+                if is_writer(ins[q]):
+                    return q
+                nop = _NOP.match(ins[q])
+                w2 = w - (int(nop.group(1)) + 1 if nop else 1)
+                if w2 > 0 and seen.get(q, 0) < w2:
+                    seen[q] = w2
+                    stack.append((q, w2))
+        return None
+
+    hazards = []
+    for d, t in enumerate(ins):
+        m = _DPP.match(t)
+        if not m:
+            continue
+        ops = m.group(2).split(",")
+        src0 = _regs(ops[1]) if len(ops) > 1 else set()
+        reads = _regs(",".join(ops[1:])) | (_regs(ops[0]) if "mac" in m.group(1) else set())
+        rules = [("dpp-src0", DPP_SRC0_WAIT, lambda u: bool(_vector_writes(u) & src0)),
+                 ("dpp-exec", DPP_EXEC_WAIT, _writes_exec_vector),
+                 ("dpp-trans", TRANS_WAIT, lambda u: u.startswith(_TRANS) and bool(_vector_writes(u) & reads))]
+        for edge_wait in (5, 11, 19):
+            rules.append(("dpp-mfma", edge_wait, lambda u, e=edge_wait: u.startswith(("v_mfma", "v_smfmac")) and _mfma_wait(u.split(None, 1)[0]) >= e
+                          and bool(_vector_writes(u) & reads)))
+        for kind, window, is_writer in rules:
+            q = writer_within(d, window, is_writer)
+            if q is not None:
+                hazards.append({"function": func_of[d], "block": (labelled[d] or ["line %d" % line_of[d]])[0], "line": line_of[d], "kind": kind,
+                                "instr": t, "writer": ins[q], "writer_line": line_of[q]})
+                break
+    return hazards
+
+
+def find_hazards(asm_text):
+    """Everything a build is rejected for."""
+    return find_exec_hazards(asm_text) + find_dpp_hazards(asm_text)
+
+
 def summary(asm_text):
     """Counts for the build record: functions, join blocks examined."""
     targets = set(m.group(1) for m in (_EXECZ.match(ln) for ln in asm_text.split("\n")) if m)
     nfunc = sum(1 for ln in asm_text.split("\n") if ln.startswith(".Lfunc_end"))
     return {"functions": nfunc, "join_blocks": len(targets)}
+
+
+def dpp_count(asm_text):
+    """DPP instructions find_dpp_hazards examines (for the build record)."""
+    return sum(1 for ln in asm_text.split("\n") if _DPP.match(ln.strip()))

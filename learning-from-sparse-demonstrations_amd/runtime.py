@@ -117,7 +117,11 @@ KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", 
 # if none is, the build FAILS (no library is better than a library whose upper lanes read stale spill slots).
 SCHEDULE_ALTERNATES = ((), ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), ("-mllvm", "-amdgpu-sched-strategy=max-memory-clause"),
                        ("-mllvm", "-amdgpu-use-amdgpu-trackers"), ("-mllvm", "-greedy-reverse-local-assignment"))
-ISA_CHECK_VERSION = 3      # (2: loop exits without a skip branch are examined too; 3: the entries of else-regions count as restores)
+# The same scan rejects a build in which a DPP instruction -- the hand-written v_fmac_f32_dpp of cpdp_common.h's fmac2_row_bcast above
+# all: the compiler's hazard recognizer does not look into an asm statement -- has too few wait states behind a vector instruction
+# that wrote its src0 or EXEC (isa_check.find_dpp_hazards): where the register allocator puts a copy-back is nothing the source controls.
+ISA_CHECK_VERSION = 4      # (2: loop exits without a skip branch are examined too; 3: the entries of else-regions count as restores;
+                           #  4: wait states in front of DPP instructions)
 
 
 def isa_record_path(lib_path):
@@ -179,18 +183,18 @@ def _checked_build(spec, out, extra=(), verbose=False, what="model"):
                 if len(asm) != 1:
                     raise LfsdError("no device assembly to check for %s %s (%s): %s" % (what, spec.name, unit, sorted(os.listdir(work))))
                 text = open(os.path.join(work, asm[0])).read()
-                hz = isa_check.find_exec_hazards(text)
+                hz = isa_check.find_exec_hazards(text) + isa_check.find_dpp_hazards(text)
                 if hz:
                     tried.append({"flags": list(alt), "hazards": len(hz), "first": hz[0]})
                     if verbose:
-                        print("isa_check: %d spill(s) before an exec restore in %s (%s, flags %s): %s" % (len(hz), spec.name, unit, list(alt), hz[0]))
+                        print("isa_check: %d spill(s) before an exec restore / DPP instruction(s) too close to a writer in %s (%s, flags %s): %s" % (len(hz), spec.name, unit, list(alt), hz[0]))
                     continue
-                record["units"][unit] = dict(isa_check.summary(text), flags=list(tuned) + list(alt), hazards=0, rejected=tried)
+                record["units"][unit] = dict(isa_check.summary(text), dpp=isa_check.dpp_count(text), flags=list(tuned) + list(alt), hazards=0, rejected=tried)
                 objs.append(obj_paths[ui])
                 built = True
                 break
             if not built:
-                raise LfsdError("every build of %s %s (%s) has VGPR spills before an exec restore (lfsd_amd/isa_check.py): %s"
+                raise LfsdError("every build of %s %s (%s) has VGPR spills before an exec restore or a DPP instruction too close to a writer (lfsd_amd/isa_check.py): %s"
                                 % (what, spec.name, unit, tried))
         link = hipcc_commands(spec, tmp, list(extra))[0][-1]
         r = subprocess.run(link, cwd=CSRC_DIR, capture_output=True, text=True)
@@ -242,7 +246,9 @@ GPU_TIER_VARIANTS = (("quadrotor", 50, "nocoarse", ("-DLFSD_COARSE_START=0",)),
                      ("quadrotor", 50, "plain", PLAIN_SCHEDULE), ("cartpole", 40, "plain", PLAIN_SCHEDULE),
                      ("rocket", 40, "plain", PLAIN_SCHEDULE), ("robotarm", 50, "plain", PLAIN_SCHEDULE),
                      # the Riccati sweep with one staging pass per split unit (tests/test_riccati_pair_stage_gpu.py)
-                     ("quadrotor", 50, "ricpair0", ("-DLFSD_RIC_PAIR_STAGE=0",)))
+                     ("quadrotor", 50, "ricpair0", ("-DLFSD_RIC_PAIR_STAGE=0",)),
+                     # the lean fp32 OC kernel with its group hand-overs through LDS (tests/test_oc_dpp_xchg_gpu.py)
+                     ("quadrotor", 50, "ocdpp0", ("-DLFSD_OC_DPP_XCHG=0",)), ("rocket", 40, "ocdpp0", ("-DLFSD_OC_DPP_XCHG=0",)))
 
 
 def build_gpu_tier_variants(verbose=False):

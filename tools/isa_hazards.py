@@ -1,5 +1,5 @@
-"""Scan the gfx950 assembly of a model library for VGPR spills placed before the exec restore of a join block
-(lfsd_amd/isa_check.py; profiles/r06_v_spill_before_exec_restore.txt).  No GPU needed.
+"""Scan the gfx950 assembly of a model library for VGPR spills placed before the exec restore of a join block and for DPP instructions
+with too few wait states behind a writer (lfsd_amd/isa_check.py; profiles/r06_v_spill_before_exec_restore.txt).  No GPU needed.
 
     python tools/isa_hazards.py <model> [extra hipcc flags ...]      compiles both translation units to assembly (tools/isa_dump.py) and scans
     python tools/isa_hazards.py --file <x.s> [...]                   scans assembly that is already there
@@ -13,8 +13,8 @@ from lfsd_amd import isa_check, runtime
 
 def report(path):
     text = open(path).read()
-    hz = isa_check.find_exec_hazards(text)
-    print("%s: %s, %d hazard(s)" % (path, isa_check.summary(text), len(hz)))
+    hz = isa_check.find_hazards(text)
+    print("%s: %s, %d DPP instruction(s), %d hazard(s)" % (path, isa_check.summary(text), isa_check.dpp_count(text), len(hz)))
     for h in hz:
         name = subprocess.run(["c++filt", h["function"] or ""], capture_output=True, text=True).stdout.strip()[:110]
         print("    %-6s %s line %d  %s   | %s" % (h["kind"], h["block"], h["line"], h["instr"][:60], name))
