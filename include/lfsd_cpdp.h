@@ -32,6 +32,9 @@
  *                         lib/QuadAlgorithm.py:616-639, where the reference has the five first-order rules (ABI 14)
  *   lfsd_group_reduce     no counterpart: the reference learns from one demonstration per run (lib/QuadAlgorithm.py:239-257); loss,
  *                         gradient and J^T J of several demonstrations per seed, summed per seed in a fixed order (ABI 15)
+ *   lfsd_aux_forward_weighted / lfsd_aux_forward_cubic_weighted / lfsd_normal_matrix_weighted   a weight per waypoint in the loss of
+ *                         lib/QuadAlgorithm.py:616-639 (the reference weighs every waypoint equally); with zero weights, demonstrations
+ *                         of different lengths in one batch, as Examples/quad_example_human_input.py collects them (ABI 16)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -40,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 15
+#define LFSD_ABI_VERSION 16
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -381,6 +384,41 @@ int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down, double l
 int lfsd_group_reduce(int dtype, int n_groups, int group_size, int n_param,
                       const void* loss, const void* grad, const void* H, const int* row_ok,
                       void* loss_g, void* grad_g, void* H_g, int* n_ok, void* stream);
+
+/* ABI 16 -- waypoint weights and ragged demonstrations in the fused loss.  wp_weight [B][n_waypoints], of arithmetic type `dtype`:
+ *   loss = sum_k w_k |y(tau_k) - wp_k|^2,   grad = sum_k w_k (y - wp_k)^T dy/dx dx/dtheta (still no factor 2),   H = sum_k w_k J_k^T J_k.
+ * A waypoint with w_k == 0 DOES NOT EXIST: its tau and its target are never read (they may be NaN, negative or beyond the horizon) and
+ * it contributes no operation to any sum -- the outputs are the bits of the unweighted call on the list without it.  That is what
+ * makes padding demonstrations of different lengths to a common n_waypoints safe.  The other waypoints enter through the scaled
+ * residual rs = w r, formed once (loss += rs r, the gradient contracts rs), and H through (w x1) x2: exact for w = 1 and for powers of
+ * two, so an array of ones gives the bits of wp_weight == NULL, which is legal and is the unweighted sibling, launch for launch
+ * (lfsd_aux_forward, lfsd_aux_forward_cubic, lfsd_normal_matrix; there is no weighted lfsd_aux_solve: call lfsd_aux_riccati[_cubic],
+ * which knows no waypoints, then one of these).  The weights must be non-negative and finite: that is the CALLER's to guarantee,
+ * nothing on the device checks it (a negative weight gives an indefinite H, a NaN weight a NaN row).  Every other argument, every
+ * LFSD_EINVAL case (before any launch) and the treatment of skipped rows are the sibling's; for lfsd_normal_matrix_weighted H must not
+ * overlap wp_weight either. */
+int lfsd_aux_forward_weighted(int dtype, int batch, int n_grid,
+                              const void* horizon, const void* auxvar, const void* consts, int const_per_traj,
+                              const void* state_grid, const void* control_grid, const void* costate_grid,
+                              const void* Z_grid,
+                              int n_waypoints, int n_iface, const int* iface_idx,
+                              const void* taus, const void* waypoints, const void* wp_weight,
+                              void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                              int substeps, double rtol, int* stats,
+                              const int* oc_status, int skip_status_mask, void* stream);
+int lfsd_aux_forward_cubic_weighted(int dtype, int batch, int n_grid,
+                                    const void* horizon, const void* auxvar, const void* consts, int const_per_traj,
+                                    const void* state_grid, const void* control_grid, const void* costate_grid,
+                                    const void* state_curv, const void* control_curv, const void* costate_curv,
+                                    const void* Z_grid,
+                                    int n_waypoints, int n_iface, const int* iface_idx,
+                                    const void* taus, const void* waypoints, const void* wp_weight,
+                                    void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                                    int substeps, double rtol, int* stats,
+                                    const int* oc_status, int skip_status_mask, void* stream);
+int lfsd_normal_matrix_weighted(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
+                                const void* auxX_grid, void* H, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

@@ -365,8 +365,10 @@ class COCSys:
         sol["state_violation_rows"] = viol_b
         return sol
 
-    def check_waypoints(self, taus, horizon, interface_idx):
-        """Host-side validation the kernels do not repeat.  The reference's opt_sol(t) is scipy's interp1d (CPDP.py:386),
+    def check_waypoints(self, taus, horizon, interface_idx, weights=None):
+        """``weights``: waypoint weights in the shape of ``taus``; entries of weight zero do not exist and are exempt (their tau may
+        be NaN or outside the horizon).
+        Host-side validation the kernels do not repeat.  The reference's opt_sol(t) is scipy's interp1d (CPDP.py:386),
         which raises ValueError for t outside [0, horizon]; its interface functions are arbitrary CasADi expressions,
         ours select state components only."""
         lib = self.compile()
@@ -377,20 +379,37 @@ class COCSys:
             idx = [int(i) for i in interface_idx]
             if any(i < 0 or i >= lib.n_state for i in idx):
                 raise LfsdError("interface_idx %s outside [0, n_state=%d)" % (idx, lib.n_state))
-        self.check_time_range(taus, horizon)
+        self.check_time_range(taus, horizon, weights)
 
     @staticmethod
-    def check_time_range(taus, horizon):
-        """scipy's interp1d raises ValueError for t outside [0, horizon] (CPDP.py:386); the kernels extrapolate: the check is here."""
+    def check_time_range(taus, horizon, weights=None):
+        """scipy's interp1d raises ValueError for t outside [0, horizon] (CPDP.py:386); the kernels extrapolate: the check is here.
+        ``weights`` (shape of ``taus``, or None): a waypoint of weight zero is never read by the kernels and is not checked."""
         tt = torch.as_tensor(taus, dtype=torch.float64).cpu() if not isinstance(taus, torch.Tensor) else taus.double().cpu()
         hz = torch.as_tensor(horizon, dtype=torch.float64).cpu() if not isinstance(horizon, torch.Tensor) else horizon.double().cpu()
         hz = hz.reshape(-1, 1) if (hz.dim() >= 1 and tt.dim() == 2 and hz.numel() == tt.shape[0]) else hz.min()
-        if tt.numel() and (bool((tt < 0).any()) or bool((tt > hz * (1 + 1e-12)).any())):
+        bad = ~((tt >= 0) & (tt <= hz * (1 + 1e-12))) if weights is not None else ((tt < 0) | (tt > hz * (1 + 1e-12)))
+        if weights is not None:      # (a NaN tau is outside the range too, unless its weight is zero)
+            ww = torch.as_tensor(weights, dtype=torch.float64).cpu() if not isinstance(weights, torch.Tensor) else weights.double().cpu()
+            bad = bad & (ww.expand_as(tt) != 0)
+        if tt.numel() and bool(bad.any()):
             raise ValueError("A value in taus is outside the interpolation range [0, horizon].")
 
+    @staticmethod
+    def check_weights(weights):
+        """Waypoint weights must be finite and non-negative (the kernels do not check: include/lfsd_cpdp.h, ABI 16).  One host read."""
+        ww = torch.as_tensor(weights, dtype=torch.float64).cpu() if not isinstance(weights, torch.Tensor) else weights.double().cpu()
+        if ww.numel() and not bool((torch.isfinite(ww) & (ww >= 0)).all()):
+            raise LfsdError("waypoint weights must be finite and non-negative")
+
     def auxSysSolverBatch(self, sol, taus=None, waypoints=None, interface_idx=None, auxvar=None, want_grids=False,
-                          Z_grid=None, out=None, phase_hook=None, validate=True, skip_status=None, interplation_level=1):
+                          Z_grid=None, out=None, phase_hook=None, validate=True, skip_status=None, interplation_level=1,
+                          waypoint_weights=None):
         """Differentiate the PMP along ``sol`` and (optionally) evaluate the sparse-waypoint loss + gradient.
+        ``waypoint_weights`` ([K] or [B, K], default None = every waypoint counts once, the launches as ever): loss =
+        sum_k w_k |y(tau_k) - wp_k|^2 and its gradient from the weighted forward sweep (``lfsd_aux_forward[_cubic]_weighted``).  A
+        weight of zero removes the waypoint: its tau and target are never read and may be NaN padding (``pad_demonstrations``).
+        Weights are checked (finite, non-negative) with ``validate``.
         ``interplation_level`` (the reference's spelling, CPDP.py:92): 1 -- along the linear interpolant of the solved grids, what
         ``cocSolver`` returns by default; 2 -- along their cubic interpolant (``cocSolver(..., interplation_level=2)``, CPDP.py:388-390):
         the curvature grids are fitted on the device (``lfsd_grid_curvature``) and the sweeps run the ``*_cubic`` entry points.
@@ -401,22 +420,33 @@ class COCSys:
         lib = self.compile()
         B = sol["state_grid"].shape[0]
         th = sol["auxvar"] if auxvar is None else self._t(auxvar, (B, lib.n_auxvar))
-        tt = wp = ii = None
+        tt = wp = ii = ww = None
+        if taus is None and waypoint_weights is not None:
+            raise LfsdError("waypoint_weights without waypoints")
         if taus is not None:
             tt = self._t(taus)
             if tt.dim() == 1:
                 tt = tt.unsqueeze(0).expand(B, -1).contiguous()
+            if waypoint_weights is not None:
+                ww = self._t(waypoint_weights)
+                if ww.dim() == 1:
+                    ww = ww.unsqueeze(0).expand(B, -1)
+                if tuple(ww.shape) != tuple(tt.shape):
+                    raise LfsdError("waypoint_weights has shape %s: [K] or [B, K] = %s as taus" % (tuple(ww.shape), tuple(tt.shape)))
+                ww = ww.contiguous()
+                if validate:
+                    self.check_weights(ww)
             wp = self._t(waypoints)
             if wp.dim() == 2:
                 wp = wp.unsqueeze(0).expand(B, -1, -1).contiguous()
             ii = None if interface_idx is None else torch.as_tensor(list(interface_idx), dtype=torch.int32, device=self._dev())
             if validate:          # (a device->host read: callers that validated at setup switch it off)
-                self.check_waypoints(tt, sol["horizon"], interface_idx)
+                self.check_waypoints(tt, sol["horizon"], interface_idx, ww)
         hz, cs, X, U, Lm = sol["horizon"], sol["consts"], sol["state_grid"], sol["control_grid"], sol["costate_grid"]
         ad = self.aux_dtype
         if ad is not None and ad != X.dtype:          # mixed precision: promote the solved grids for the aux pass
             cv = lambda t: None if t is None else t.to(ad).contiguous()
-            hz, th, cs, X, U, Lm, tt, wp = (cv(t) for t in (hz, th, cs, X, U, Lm, tt, wp))
+            hz, th, cs, X, U, Lm, tt, wp, ww = (cv(t) for t in (hz, th, cs, X, U, Lm, tt, wp, ww))
         status = sol.get("status")
         if skip_status is None:
             skip_status = (4,)
@@ -424,7 +454,7 @@ class COCSys:
             skip_status = ()
         return lib.aux_solve(hz, th, cs, X, U, Lm, tt, wp, ii, substeps=self.aux_substeps, want_grids=want_grids,
                              Z_grid=Z_grid, out=out, phase_hook=phase_hook, rtol=self.aux_rtol, oc_status=status,
-                             skip_status=skip_status, interp_level=interplation_level)
+                             skip_status=skip_status, interp_level=interplation_level, **({} if ww is None else dict(wp_weight=ww)))
 
     def _times(self, times, dtype, batch):
         tt = times if isinstance(times, torch.Tensor) else torch.as_tensor(np.asarray(times, dtype=np.float64))
@@ -588,6 +618,44 @@ class COCSys_TimeVarying(COCSys):
     time_varying = True
 
 
+def pad_demonstrations(taus_list, waypoints_list, weights_list=None):
+    """Ragged demonstrations as one batch: ``taus_list[d]`` (K_d times) and ``waypoints_list[d]`` ([K_d, n_iface] targets), optionally
+    ``weights_list[d]`` (K_d weights; default 1 each), padded to K = max K_d.  Returns float64 numpy arrays ``(taus [D, K], waypoints
+    [D, K, n_iface], weights [D, K])``: the padding has weight 0 and NaN in ``taus`` and ``waypoints``.  The NaN is deliberate -- a
+    waypoint of weight zero is never read by the kernels (include/lfsd_cpdp.h, ABI 16), and a kernel that did read one would show.
+    Hand the three to ``SparseDemoLearner(..., taus, waypoints, ..., waypoint_weights=weights)`` or ``auxSysSolverBatch``."""
+    D = len(taus_list)
+    if D == 0 or len(waypoints_list) != D or (weights_list is not None and len(weights_list) != D):
+        raise LfsdError("pad_demonstrations takes one entry per demonstration in every list (got %d, %d%s)"
+                        % (D, len(waypoints_list), "" if weights_list is None else ", %d" % len(weights_list)))
+    tl = [np.asarray(t, dtype=np.float64).reshape(-1) for t in taus_list]
+    wl = []
+    for d, (w, t) in enumerate(zip(waypoints_list, tl)):
+        w = np.asarray(w, dtype=np.float64)
+        if len(t) == 0:
+            w = np.zeros((0, 0))
+        elif w.ndim != 2 or w.shape[0] != len(t) or w.shape[1] == 0:
+            raise LfsdError("demonstration %d: %d times and targets of shape %s ([K_d, n_iface])" % (d, len(t), w.shape))
+        wl.append(w)
+    ni = max(w.shape[1] for w in wl)
+    K = max(len(t) for t in tl)
+    if K == 0 or ni == 0:
+        raise LfsdError("pad_demonstrations: no demonstration has a waypoint")
+    taus, wps, wts = np.full((D, K), np.nan), np.full((D, K, ni), np.nan), np.zeros((D, K))
+    for d, (t, w) in enumerate(zip(tl, wl)):
+        k = len(t)
+        if k and w.shape != (k, ni):
+            raise LfsdError("demonstration %d: %d times and targets of shape %s (interface of %d outputs)" % (d, k, w.shape, ni))
+        wt = np.ones(k) if weights_list is None else np.asarray(weights_list[d], dtype=np.float64).reshape(-1)
+        if len(wt) != k:
+            raise LfsdError("demonstration %d: %d times and %d weights" % (d, k, len(wt)))
+        taus[d, :k], wts[d, :k] = t, wt
+        if k:
+            wps[d, :k] = w
+    COCSys.check_weights(wts)
+    return taus, wps, wts
+
+
 class SparseDemoLearner:
     """The outer learning iteration of the examples, batched on the device.
 
@@ -703,14 +771,35 @@ class SparseDemoLearner:
     initialised ``torch.distributed`` (no all-reduce is issued), a sequence for ``true_loss_print_flag``, a batch that is no whole
     number of groups, ``demos_per_seed`` with another mode, a ``theta0`` or per-group sequence of the wrong length (DESIGN.md
     section 15).
+
+    ``waypoint_weights`` / ``n_waypoints`` (default ``None`` for both = every waypoint counts once, the launches the learner always
+    made, through the unweighted entry points): a weight per waypoint in the fused loss, ``loss = sum_k w_k |y(tau_k) - wp_k|^2`` with
+    its gradient and, for ``method="LM"``, ``H = sum_k w_k J_k^T J_k`` (``lfsd_aux_forward[_cubic]_weighted``,
+    ``lfsd_normal_matrix_weighted``; the same number of launches).  Weights come in the shapes ``taus`` comes in -- [K], [B, K], in
+    grouped mode [D, K] tiled over the seeds -- and are checked once, here: finite and non-negative.  A weight of ZERO removes the
+    waypoint: its ``tau`` and target are never read (they may be NaN or outside the horizon) and it adds no operation to any sum, so a
+    row that keeps k of its K waypoints walks, bit for bit, the path it walks in a learner built with those k alone -- ragged
+    demonstrations share one batch (``pad_demonstrations`` pads Python lists with NaN and weight 0).  ``n_waypoints`` (integers: a
+    scalar, [B], or [D] in grouped mode) is shorthand for weight 1 below the count and 0 from it on.  All-ones weights give the bits
+    of no weights.  It combines with the three modes (in shared mode the all-reduce still carries p + 2 numbers), the five rules, the
+    rows path and ``"LM"``, ``interplation_level=2``, ``warm_start``, ``skip_unconverged``, ``trace``, ``true_loss_print_flag`` (the
+    second evaluation uses the same weights) and ``stop_rule`` (the weights move to the dense batch with ``taus`` and ``waypoints``).
+    Refused with ``LfsdError``: together with ``loss_fn`` (a user loss does its own weighting), both arguments at once, negative or
+    non-finite weights, a shape that is none of the above, a count outside [0, K].
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
                  learning_rate=1e-2, mu=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-8, proj_lo=None, consts=None,
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
                  skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None,
-                 lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8, demos_per_seed=None):
+                 lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8, demos_per_seed=None,
+                 waypoint_weights=None, n_waypoints=None):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
+        if waypoint_weights is not None and n_waypoints is not None:
+            raise LfsdError("waypoint_weights and n_waypoints are two spellings of one array (n_waypoints: weight 1 below the count, 0 "
+                            "from it on): give one")
+        if loss_fn is not None and (waypoint_weights is not None or n_waypoints is not None):
+            raise LfsdError("waypoint_weights / n_waypoints weigh the fused loss: a loss_fn does its own weighting")
         self.demos_per_seed = self.n_groups = None
         if demos_per_seed is not None and mode != "grouped":
             raise LfsdError("demos_per_seed belongs to mode='grouped' (mode=%r gives every row %s)"
@@ -772,13 +861,14 @@ class SparseDemoLearner:
         tt = oc._t(taus)
         self.taus = tt.unsqueeze(0).expand(B, -1).contiguous() if tt.dim() == 1 else tt
         if loss_fn is not None and waypoints is None:      # (a user-written loss keeps its own targets)
-            self.wps, self.iface = None, None
+            self.wps, self.iface, self.wts = None, None, None
             oc.check_time_range(self.taus, self.hz)
         else:
             wp = oc._t(waypoints)
             self.wps = wp.unsqueeze(0).expand(B, -1, -1).contiguous() if wp.dim() == 2 else wp
             self.iface = None if interface_idx is None else torch.as_tensor(list(interface_idx), dtype=torch.int32, device=self.x0.device)
-            oc.check_waypoints(self.taus, self.hz, interface_idx)
+            self.wts = self._init_weights(waypoint_weights, n_waypoints)
+            oc.check_waypoints(self.taus, self.hz, interface_idx, self.wts)
         th = oc._t(theta0)
         th = th.unsqueeze(0) if th.dim() == 1 else th
         if mode == "shared":
@@ -856,6 +946,47 @@ class SparseDemoLearner:
             self._prev = None            # (controls, status) of the previous solve of the rows now active, dense
             self._loss_full = self._grad_full = None
         self.n_active = B
+
+    # ---- waypoint weights and ragged demonstrations (ABI 16) ----------------------------------------------------------------
+    def _init_weights(self, weights, counts):
+        """[B, K] weights in the dtype of ``taus`` on the device, or None when neither argument is given (the unweighted launches).
+        Accepted in the shapes ``taus`` is: [K], [B, K], in grouped mode [D, K] tiled over the seeds; ``counts`` (n_waypoints):
+        integers, a scalar, [B] or [D].  Checked here, once: finite and non-negative; counts inside [0, K]."""
+        if weights is None and counts is None:
+            return None
+        B, K = self.taus.shape
+        D = self.demos_per_seed
+        lead = (B,) if D is None else (B, D)
+        tile = lambda t: t if t.shape[0] == B else t.repeat((B // D,) + (1,) * (t.dim() - 1))
+        if counts is not None:
+            c = counts.detach().cpu() if isinstance(counts, torch.Tensor) else torch.as_tensor(np.asarray(counts))
+            if c.dtype == torch.bool or c.is_floating_point() and not bool((c == c.round()).all()):
+                raise LfsdError("n_waypoints counts waypoints: integers (got %r)" % (counts,))
+            c = c.to(torch.int64)
+            if c.dim() == 0:
+                c = c.expand(B)
+            elif c.dim() == 1 and c.shape[0] in lead:
+                c = tile(c)
+            else:
+                raise LfsdError("n_waypoints has shape %s: a scalar or one count per row, leading dimension in %s" % (tuple(c.shape), lead))
+            if bool((c < 0).any()) or bool((c > K).any()):
+                raise LfsdError("n_waypoints outside [0, K = %d]: %s" % (K, c.tolist()))
+            w = (torch.arange(K).unsqueeze(0) < c.unsqueeze(1)).to(torch.float64)
+        else:
+            w = weights.detach().double().cpu() if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights, dtype=np.float64))
+            if w.dim() == 1 and w.shape[0] == K:
+                w = w.unsqueeze(0).expand(B, K)
+            elif w.dim() == 2 and w.shape[1] == K and w.shape[0] in lead:
+                w = tile(w)
+            else:
+                raise LfsdError("waypoint_weights has shape %s: [K] or [rows, K] with K = %d and rows in %s, as taus"
+                                % (tuple(w.shape), K, lead))
+            self.oc.check_weights(w)
+        return w.to(device=self.taus.device, dtype=self.taus.dtype).contiguous()
+
+    def _wkw(self, wts):
+        """The keyword that carries the weights into auxSysSolverBatch; without weights the call is what it always was."""
+        return {} if wts is None else dict(waypoint_weights=wts)
 
     # ---- per-row update rules (hyper-parameter sweeps in one batch) and device traces -------------------------------------
     @staticmethod
@@ -969,11 +1100,13 @@ class SparseDemoLearner:
             self.lib.trace_append(self.iter_idx - 1, loss.contiguous(), grad.contiguous(), self.theta, loss_trace=self.loss_trace,
                                   gnorm_trace=self.grad_norm_trace, theta_trace=self.theta_trace, row_active=row_active)
 
-    def _normal_matrix(self, aux, hz, taus):
-        """H = J^T J [rows, p, p] of the evaluation `aux` (sensitivity grids written), in the sweeps' dtype, cast to theta's."""
+    def _normal_matrix(self, aux, hz, taus, wts=None):
+        """H = J^T J [rows, p, p] of the evaluation `aux` (sensitivity grids written), in the sweeps' dtype, cast to theta's.
+        `wts`: the rows' waypoint weights (H = sum_k w_k J_k^T J_k), or None."""
         aX = aux["auxX_grid"]
         cv = lambda t: t.to(aX.dtype).contiguous()
-        return self.lib.normal_matrix(cv(hz), cv(taus), aX, self.iface).to(self.theta.dtype)
+        kw = {} if wts is None else dict(wp_weight=cv(wts))
+        return self.lib.normal_matrix(cv(hz), cv(taus), aX, self.iface, **kw).to(self.theta.dtype)
 
     lm_lambda = property(lambda self: None if self._lm is None else self._lm["lam"], doc="[B] damping of every seed (method='LM')")
     lm_loss = property(lambda self: None if self._lm is None else self._lm["loss"],
@@ -1034,12 +1167,12 @@ class SparseDemoLearner:
         self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, want_grids=lm, Z_grid=self._Z,
                                               out=self._aux_out(), phase_hook=phase, validate=False,
                                               skip_status=(3, 4) if self.skip_unconverged else None,
-                                              interplation_level=self.interplation_level)
+                                              interplation_level=self.interplation_level, **self._wkw(self.wts))
         self._Z = self._aux["Z_grid"]
         if lm:
             if hook is not None:
                 hook("normal_matrix")
-            self._H_t = self._normal_matrix(self._aux, self.hz, self.taus)
+            self._H_t = self._normal_matrix(self._aux, self.hz, self.taus, self.wts)
         loss, grad = self._aux["loss"].to(self.theta.dtype), self._aux["grad"].to(self.theta.dtype)
         if self.skip_unconverged:
             loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
@@ -1143,11 +1276,11 @@ class SparseDemoLearner:
         aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, want_grids=lm, Z_grid=full["Z"][:n],
                                         out={k: full["aux"][k][:n] for k in ("loss", "grad", "stats")}, phase_hook=phase,
                                         validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
-                                        interplation_level=self.interplation_level)
+                                        interplation_level=self.interplation_level, **self._wkw(d["wts"][:n] if "wts" in d else None))
         if lm:      # H of the dense rows goes to its seeds' rows of the full-size matrix, as loss and gradient do
             if hook is not None:
                 hook("normal_matrix")
-            lib.scatter_rows(rows, self._normal_matrix(aux, d["hz"][:n], d["taus"][:n]).contiguous(), self._H_full, n)
+            lib.scatter_rows(rows, self._normal_matrix(aux, d["hz"][:n], d["taus"][:n], d["wts"][:n] if "wts" in d else None).contiguous(), self._H_full, n)
             self._H_t = self._H_full
         self._sol_active, self._aux_active = sol, aux
         self._prev = (sol["control_grid"], sol["status"])
@@ -1176,6 +1309,8 @@ class SparseDemoLearner:
             src = dict(x0=self.x0, hz=self.hz, taus=self.taus, wps=self.wps)
             if self.consts is not None and self.consts.dim() == 2:
                 src["consts"] = self.consts
+            if self.wts is not None:      # (the weights are gathered with taus and waypoints when the set shrinks)
+                src["wts"] = self.wts
             self._dense = {k: torch.empty_like(t) for k, t in src.items()}
             self._dense.update(theta=torch.empty_like(self.theta), sources=src)
             self._prev = (self._sol["control_grid"], self._sol["status"])

@@ -125,7 +125,9 @@ class QuadAlgorithm(object):
             raise Exception("Wrong optimization method type!")
 
     def run(self, QuadInitialCondition, QuadDesiredStates, SparseInput, ObsList=(), print_flag=False, save_flag=False,
-            initial_parameters=None, save_dir=None, stop="all", sample_all=False):
+            initial_parameters=None, save_dir=None, stop="all", sample_all=False, waypoint_weights=None):
+        """``waypoint_weights`` ([K], or [S, K] with S seeds; default None): handed to ``SparseDemoLearner`` -- a confidence per
+        waypoint, zero removes it (CPDP.SparseDemoLearner)."""
         if stop not in ("all", "per_seed"):
             raise ValueError("stop must be 'all' or 'per_seed'")
         t0 = time.time()
@@ -144,6 +146,7 @@ class QuadAlgorithm(object):
                                               self.time_horizon, self.time_list_sparse, self.waypoints,
                                               self.interface_pos_idx, theta0, method=self.optimization_method_str,
                                               learning_rate=self.learning_rate, **self.opt_kwargs,
+                                              **({} if waypoint_weights is None else dict(waypoint_weights=waypoint_weights)),
                                               **(dict(stop_rule=dict(loss=0.9, grad_norm=0.05)) if stop == "per_seed" else {}))
         self.loss_trace, self.parameter_trace = [], [self.learner.theta.cpu().numpy().copy()]
         loss, diff_loss_norm = 100.0, 100.0
@@ -187,7 +190,8 @@ class QuadAlgorithm(object):
                         {'results': results})
         return results
 
-    def run_comparison(self, para_list, QuadInitialCondition, QuadDesiredStates, SparseInput, initial_parameters=None):
+    def run_comparison(self, para_list, QuadInitialCondition, QuadDesiredStates, SparseInput, initial_parameters=None,
+                       waypoint_weights=None):
         """The comparison scripts of the reference (test/opt_methods_comparison.py, test/*_learning_rate_comparison.py: one
         ``load_optimization_function`` + ``run`` per configuration, the loss traces overlaid) as ONE batch.  ``para_list``: the
         dictionaries ``load_optimization_function`` takes, with equal ``iter_num`` (else ``ValueError``); ``initial_parameters``: one
@@ -201,6 +205,7 @@ class QuadAlgorithm(object):
           ``label_list``             the method names when the methods differ, else ``str(learning_rate)`` -- the scripts' labels;
           ``parameter_trace``        per configuration [stop_iter + 1, 7] or [iters + 1, S, 7];
           ``stop_iter``              per configuration the iterations it took, an int or [S] (0: still learning at ``iter_num``).
+        ``waypoint_weights`` ([K], default None): a weight per waypoint for every row, handed to ``SparseDemoLearner``.
         Plotting stays with the caller (``plot_opt_method_comparison`` is UI)."""
         para_list = list(para_list)
         if not para_list:
@@ -228,7 +233,8 @@ class QuadAlgorithm(object):
         per_row = {k: [v for v in vals for _ in range(S)] for k, vals in rows.items()}
         self.learner = CPDP.SparseDemoLearner(self.oc, np.tile(self.ini_state, (C * S, 1)), self.time_horizon, self.time_list_sparse,
                                               self.waypoints, self.interface_pos_idx, np.tile(seeds, (C, 1)),
-                                              stop_rule=dict(loss=0.9, grad_norm=0.05), trace=K, **per_row)
+                                              stop_rule=dict(loss=0.9, grad_norm=0.05), trace=K, **per_row,
+                                              **({} if waypoint_weights is None else dict(waypoint_weights=waypoint_weights)))
         for _ in range(K):
             if self.learner.n_active == 0:
                 break

@@ -60,6 +60,16 @@ template <typename T> struct AuxArgsCubic : AuxArgs<T> {
   const T* costate_curv;          // [B][N+1][NX]
 };
 
+// Waypoint weights (ABI 16): loss = sum_k w_k |y(tau_k) - wp_k|^2.  The weighted forward sweeps are instantiations of their own with
+// argument structs of their own: the unweighted kernels keep their arguments and their code as they are, instruction for
+// instruction.  wp_weight is never NULL here -- a NULL weight array is served by the unweighted kernel.
+template <typename T> struct AuxArgsWeighted : AuxArgs<T> {
+  const T* wp_weight;             // [B][n_waypoints], non-negative and finite (the caller's to guarantee); 0: the waypoint does not exist
+};
+template <typename T> struct AuxArgsCubicWeighted : AuxArgsCubic<T> {
+  const T* wp_weight;
+};
+
 // LAY: which packing of the staged coefficients the kernel uses (codegen: 0 Riccati sweep, every matrix; 1 forward sweep,
 // without Hxx / Hxe) -- the node stride NCOEF and every offset behind it follow
 // NSLOT: node slots in LDS -- NNODE (one split unit), or 2 NNODE - 1 where the Riccati sweep stages the nodes of two consecutive
@@ -758,5 +768,22 @@ template <class M, typename T, int G, int LAY, int LVL> LFSD_DEV void aux_setup(
 #undef LFSD_AUX_ARGS
 #undef LFSD_AUX_RICCATI_KERNEL
 #undef LFSD_AUX_FORWARD_KERNEL
+// ... and the forward sweeps of both levels with a weight per waypoint (the Riccati sweep knows no waypoints: not included again)
+#define LFSD_AUX_WEIGHTED 1
+#define LFSD_AUX_LVL 1
+#define LFSD_AUX_ARGS AuxArgsWeighted
+#define LFSD_AUX_FORWARD_KERNEL aux_forward_weighted_kernel
+#include "cpdp_aux_sweeps.inc"
+#undef LFSD_AUX_LVL
+#undef LFSD_AUX_ARGS
+#undef LFSD_AUX_FORWARD_KERNEL
+#define LFSD_AUX_LVL 2
+#define LFSD_AUX_ARGS AuxArgsCubicWeighted
+#define LFSD_AUX_FORWARD_KERNEL aux_forward_cubic_weighted_kernel
+#include "cpdp_aux_sweeps.inc"
+#undef LFSD_AUX_LVL
+#undef LFSD_AUX_ARGS
+#undef LFSD_AUX_FORWARD_KERNEL
+#undef LFSD_AUX_WEIGHTED
 
 }  // namespace lfsd

@@ -3,9 +3,11 @@
 //   LFSD_AUX_LVL              1 (linear interpolant, CPDP.py:386) or 2 (cubic, CPDP.py:388-390)
 //   LFSD_AUX_ARGS             the kernels' argument struct (AuxArgs / AuxArgsCubic)
 //   LFSD_AUX_RICCATI_KERNEL, LFSD_AUX_FORWARD_KERNEL   their names
+//   LFSD_AUX_WEIGHTED         defined (ABI 16): the forward kernel alone, with a weight per waypoint (a.wp_weight, never NULL)
 // One text, two pairs of kernels -- and not one function template that two thin kernels call: the sweeps leave early (a skipped row, a
 // wrong launch shape), and a `return` of an inlined function is a branch the optimiser treats differently from a kernel's own.  The
 // level-1 kernels must stay instruction for instruction what they were before level 2 existed (DESIGN.md section 11).
+#ifndef LFSD_AUX_WEIGHTED
 template <class M, typename T, int G>
 __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) LFSD_AUX_RICCATI_KERNEL(LFSD_AUX_ARGS<T> a) {
   constexpr int LVL = LFSD_AUX_LVL;
@@ -263,10 +265,16 @@ __global__ void __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) LFSD_AUX_RICCATI
   }
   if (valid && a.stats && lane == 0) { a.stats[traj * 4 + 0] = n_units; a.stats[traj * 4 + 1] = n_unmet; }
 }
+#endif  // LFSD_AUX_WEIGHTED
 
 template <class M, typename T, int G>
 __global__ void __launch_bounds__(64, 1) LFSD_AUX_FORWARD_KERNEL(LFSD_AUX_ARGS<T> a) {
   constexpr int LVL = LFSD_AUX_LVL;
+#ifdef LFSD_AUX_WEIGHTED
+  constexpr bool WTD = true;
+#else
+  constexpr bool WTD = false;
+#endif
   if (blockDim.x != 64) return;                   // one wavefront per workgroup: see the note above aux_riccati_kernel
   using Ctx = AuxCtx<M, T, G, 1, LVL>;
   using Lay = AuxLayout<M, 1>;
@@ -443,7 +451,15 @@ __global__ void __launch_bounds__(64, 1) LFSD_AUX_FORWARD_KERNEL(LFSD_AUX_ARGS<T
     // loss and gradient contributions of the waypoints that fall into this interval
     // (opt_sol(tau) on the interpolant of the level -- linear, CPDP.py:386, or cubic, :388-390; auxsys_sol(tau) is the linear
     //  interpolant of its grid values at either level: CPDP.py:381 calls interpolation() at its default level)
+    // (weighted kernels, ABI 16: loss = sum w |r|^2 and gradient sum w r^T dy/dx X through the scaled residual rs = w r, formed once
+    //  -- exact for w = 1 and for powers of two, so all-ones weights give the bits of the unweighted kernel; a waypoint of weight 0 does
+    //  not exist: its tau and its target are never read)
     for (int w = 0; w < a.n_waypoints; ++w) {
+      T wk = T(1);
+      if constexpr (WTD) {
+        wk = a.wp_weight[traj * a.n_waypoints + w];
+        if (wk == T(0)) continue;
+      }
       const T tau = a.taus[traj * a.n_waypoints + w];
       int kw = (int)t_floor(tau / s.dgrid);
       kw = kw < 0 ? 0 : (kw > N - 1 ? N - 1 : kw);
@@ -463,12 +479,23 @@ __global__ void __launch_bounds__(64, 1) LFSD_AUX_FORWARD_KERNEL(LFSD_AUX_ARGS<T
 #pragma unroll
           for (int i = 0; i < NX; ++i) cur[i] = s.state_at(i, sw);
           M::iface(cur, s.c, y);
+          if constexpr (WTD) {
+            T rs[M::NIF];
+#pragma unroll
+            for (int q = 0; q < M::NIF; ++q) {
+              r[q] = y[q] - a.waypoints[(traj * a.n_waypoints + w) * M::NIF + q];
+              rs[q] = wk * r[q];
+              loss += rs[q] * r[q];
+            }
+            M::iface_vjp(cur, s.c, rs, rvec);
+          } else {
 #pragma unroll
           for (int q = 0; q < M::NIF; ++q) {
             r[q] = y[q] - a.waypoints[(traj * a.n_waypoints + w) * M::NIF + q];
             loss += r[q] * r[q];
           }
           M::iface_vjp(cur, s.c, r, rvec);
+          }
         }
       }
       for (int q = 0; q < (compiled_iface ? 0 : a.n_iface); ++q) {
@@ -479,8 +506,14 @@ __global__ void __launch_bounds__(64, 1) LFSD_AUX_FORWARD_KERNEL(LFSD_AUX_ARGS<T
           if (i == idx) {
             const T cur = s.state_at(i, sw);
             const T r = cur - target;
+            if constexpr (WTD) {
+              const T rs = wk * r;
+              rvec[i] += rs;
+              loss += rs * r;
+            } else {
             rvec[i] += r;
             loss += r * r;
+            }
           }
         }
       }

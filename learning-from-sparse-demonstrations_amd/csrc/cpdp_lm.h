@@ -19,6 +19,7 @@ template <typename T> struct NormalMatrixArgs {
   const T* taus;          // [B][K]
   const T* auxX_grid;     // [B][n_grid+1][p][n]
   T* H;                   // [B][p][p]   (must not alias an input)
+  const T* wp_weight;     // [B][K] or nullptr (ABI 16): H = sum_k w_k J_k^T J_k; a waypoint of weight 0 does not exist (its tau is not read)
 };
 
 // H[b][q1][q2] = sum_k sum_c X(tau_k)[q1][idx_c] X(tau_k)[q2][idx_c], X the linear interpolant of auxX_grid (interval rule of
@@ -26,7 +27,8 @@ template <typename T> struct NormalMatrixArgs {
 // lower triangle (q2 <= q1) sums -- waypoints ascending, then interface components ascending -- and stores the element and its mirror
 // image: both triangles hold the same bits.  The threads above the diagonal leave at once.  An interface index outside [0, n_state)
 // is seen by every thread of the launch (the list is shared by the batch): nothing is written.  A few hundred bytes per trajectory:
-// the launch is latency, not bandwidth.
+// the launch is latency, not bandwidth.  Symmetry with weights: w x1 x2 is formed as (w x1) x2 by the one thread that stores both
+// images, so which factor carries the weight cannot show.
 template <typename T> __global__ void __launch_bounds__(256) normal_matrix_kernel(NormalMatrixArgs<T> a) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int N = a.n_grid, n = a.n_state, p = a.n_param, K = a.n_waypoints, C = a.n_iface;
@@ -44,7 +46,15 @@ template <typename T> __global__ void __launch_bounds__(256) normal_matrix_kerne
   const T* X2 = a.auxX_grid + (traj * (long long)(N + 1) * p + q2) * n;
   const long long node = (long long)p * n;
   T acc = T(0);
+  // (weights: on ONE factor of each product, scaled once -- exact for w = 1 and for powers of two, so all-ones weights give the bits of
+  //  the unweighted call; the thread of the lower triangle still stores both mirror images)
+  const bool weighted = a.wp_weight != nullptr;
   for (int w = 0; w < K; ++w) {
+    T wk = T(1);
+    if (weighted) {
+      wk = a.wp_weight[traj * K + w];
+      if (wk == T(0)) continue;
+    }
     const T tau = a.taus[traj * K + w];
     const int k = sample_interval(tau, h, N);
     const T s = (tau - T(k) * h) / h;
@@ -54,7 +64,8 @@ template <typename T> __global__ void __launch_bounds__(256) normal_matrix_kerne
       const int i = a.iface_idx[c];
       const T x1 = a1[i] + s * (a1[node + i] - a1[i]);
       const T x2 = a2[i] + s * (a2[node + i] - a2[i]);
-      acc += x1 * x2;
+      if (weighted) acc += (wk * x1) * x2;
+      else acc += x1 * x2;
     }
   }
   a.H[traj * pp + (long long)q1 * p + q2] = acc;

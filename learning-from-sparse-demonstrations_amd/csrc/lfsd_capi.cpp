@@ -301,7 +301,8 @@ static int aux_phase_t(int phases, int batch, int n_grid, const void* horizon, c
                        void* Z_grid, int n_waypoints, int n_iface, const int* iface_idx, const void* taus,
                        const void* waypoints, void* loss, void* grad, void* auxX_grid, void* auxU_grid, int substeps,
                        double rtol, int* stats, const int* oc_status, int skip_mask, void* stream,
-                       const void* state_curv = nullptr, const void* control_curv = nullptr, const void* costate_curv = nullptr) {
+                       const void* state_curv = nullptr, const void* control_curv = nullptr, const void* costate_curv = nullptr,
+                       const void* wp_weight = nullptr) {
   // (interpolation level 2 when the three curvature grids are given: the level-1 launches take the AuxArgs base, as ever)
   lfsd::AuxArgsCubic<T> a;
   const bool cubic = state_curv != nullptr;
@@ -351,6 +352,10 @@ static int aux_phase_t(int phases, int batch, int n_grid, const void* horizon, c
     constexpr int GF = lfsd::fwd_lanes<Model>() < G ? lfsd::fwd_lanes<Model>() : G;
     constexpr int GPBF = 64 / GF;
     const unsigned grid_f = (unsigned)(((long long)batch + GPBF - 1) / GPBF);
+    if (wp_weight) {      // (ABI 16: the weighted sweeps are kernels of their own; without weights the launches below, as ever)
+      if constexpr (sizeof(T) == 4) return lfsd_detail::launch_forward_weighted_f32(grid_f, stream, a, cubic, (const float*)wp_weight);
+      else return lfsd_detail::launch_forward_weighted_f64(grid_f, stream, a, cubic, (const double*)wp_weight);
+    }
     if (cubic) {
       if constexpr (sizeof(T) == 4) return lfsd_detail::launch_forward_cubic_f32(grid_f, stream, a);
       else return lfsd_detail::launch_forward_cubic_f64(grid_f, stream, a);
@@ -368,7 +373,7 @@ static int aux_dispatch(int phases, int dtype, int batch, int n_grid, const void
                         const void* taus, const void* waypoints, void* loss, void* grad, void* auxX_grid,
                         void* auxU_grid, int substeps, double rtol, int* stats, const int* oc_status, int skip_mask,
                         void* stream, int level = 1, const void* state_curv = nullptr, const void* control_curv = nullptr,
-                        const void* costate_curv = nullptr) {
+                        const void* costate_curv = nullptr, const void* wp_weight = nullptr) {
   if (level == 2 && (!state_curv || !control_curv || !costate_curv || n_grid < 3)) return LFSD_EINVAL;      // (scipy's cubic needs four nodes)
   if (level != 2) state_curv = control_curv = costate_curv = nullptr;
   if (batch <= 0 || n_grid <= 0 || n_waypoints < 0 || n_iface < 0 || substeps < 0 || !(rtol >= 0)) return LFSD_EINVAL;
@@ -383,12 +388,12 @@ static int aux_dispatch(int phases, int dtype, int batch, int n_grid, const void
     return aux_phase_t<float>(phases, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
                               costate_grid, Z_grid, n_waypoints, n_iface, iface_idx, taus, waypoints, loss, grad,
                               auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream, state_curv, control_curv,
-                              costate_curv);
+                              costate_curv, wp_weight);
   if (dtype == LFSD_F64)
     return aux_phase_t<double>(phases, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid,
                                control_grid, costate_grid, Z_grid, n_waypoints, n_iface, iface_idx, taus, waypoints,
                                loss, grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_mask, stream, state_curv,
-                               control_curv, costate_curv);
+                               control_curv, costate_curv, wp_weight);
   return LFSD_EINVAL;
 }
 
@@ -584,6 +589,34 @@ LFSD_API int lfsd_aux_forward_cubic(int dtype, int batch, int n_grid, const void
                       control_curv, costate_curv);
 }
 
+// ---- ABI 16: a weight per waypoint in the fused loss.  wp_weight == NULL is the unweighted sibling, launch for launch ----
+LFSD_API int lfsd_aux_forward_weighted(int dtype, int batch, int n_grid, const void* horizon, const void* auxvar,
+                                       const void* consts, int const_per_traj, const void* state_grid,
+                                       const void* control_grid, const void* costate_grid, const void* Z_grid, int n_waypoints,
+                                       int n_iface, const int* iface_idx, const void* taus, const void* waypoints,
+                                       const void* wp_weight, void* loss, void* grad, void* auxX_grid, void* auxU_grid,
+                                       int substeps, double rtol, int* stats, const int* oc_status, int skip_status_mask,
+                                       void* stream) {
+  return aux_dispatch(2, dtype, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
+                      costate_grid, const_cast<void*>(Z_grid), n_waypoints, n_iface, iface_idx, taus, waypoints, loss,
+                      grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_status_mask, stream, 1, nullptr, nullptr,
+                      nullptr, n_waypoints > 0 ? wp_weight : nullptr);
+}
+
+LFSD_API int lfsd_aux_forward_cubic_weighted(int dtype, int batch, int n_grid, const void* horizon, const void* auxvar,
+                                             const void* consts, int const_per_traj, const void* state_grid,
+                                             const void* control_grid, const void* costate_grid, const void* state_curv,
+                                             const void* control_curv, const void* costate_curv, const void* Z_grid,
+                                             int n_waypoints, int n_iface, const int* iface_idx, const void* taus,
+                                             const void* waypoints, const void* wp_weight, void* loss, void* grad,
+                                             void* auxX_grid, void* auxU_grid, int substeps, double rtol, int* stats,
+                                             const int* oc_status, int skip_status_mask, void* stream) {
+  return aux_dispatch(2, dtype, batch, n_grid, horizon, auxvar, consts, const_per_traj, state_grid, control_grid,
+                      costate_grid, const_cast<void*>(Z_grid), n_waypoints, n_iface, iface_idx, taus, waypoints, loss,
+                      grad, auxX_grid, auxU_grid, substeps, rtol, stats, oc_status, skip_status_mask, stream, 2, state_curv,
+                      control_curv, costate_curv, n_waypoints > 0 ? wp_weight : nullptr);
+}
+
 // curvature grids of the not-a-knot cubic spline through each component of a grid (cpdp_spline.h)
 LFSD_API int lfsd_grid_curvature(int dtype, int batch, int n_grid, int n_comp, const void* grid, void* curv, void* stream) {
   if (batch <= 0 || n_grid < 3 || n_comp <= 0 || !grid || !curv || grid == curv) return LFSD_EINVAL;
@@ -698,26 +731,41 @@ LFSD_API int lfsd_trace_append(int dtype, int batch, int n_param, int iter_idx, 
 }
 
 // ---- ABI 14: Levenberg-Marquardt outer update from per-seed Gauss-Newton matrices (cpdp_lm.h; no counterpart in the reference) ----
-LFSD_API int lfsd_normal_matrix(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
-                                const int* iface_idx, const void* horizon, const void* taus, const void* auxX_grid, void* H,
-                                void* stream) {
+static int normal_matrix_dispatch(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                  const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
+                                  const void* auxX_grid, void* H, void* stream) {
   if (batch <= 0 || n_grid < 1 || n_state <= 0 || n_param <= 0 || n_waypoints <= 0 || n_iface <= 0) return LFSD_EINVAL;
   if (!iface_idx || !horizon || !taus || !auxX_grid || !H) return LFSD_EINVAL;
   if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
   const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, P = (unsigned long long)n_param;
   const unsigned long long hb = B * P * P * es;
   if (spans_overlap(H, hb, iface_idx, (unsigned long long)n_iface * sizeof(int)) || spans_overlap(H, hb, horizon, B * es) ||
-      spans_overlap(H, hb, taus, B * n_waypoints * es) ||
+      spans_overlap(H, hb, taus, B * n_waypoints * es) || spans_overlap(H, hb, wp_weight, B * n_waypoints * es) ||
       spans_overlap(H, hb, auxX_grid, B * (unsigned long long)(n_grid + 1) * P * n_state * es))
     return LFSD_EINVAL;
   if (dtype == LFSD_F32) {
     lfsd::NormalMatrixArgs<float> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const float*)horizon,
-                                    (const float*)taus, (const float*)auxX_grid, (float*)H};
+                                    (const float*)taus, (const float*)auxX_grid, (float*)H, (const float*)wp_weight};
     return lfsd_detail::launch_normal_matrix_f32(a, stream);
   }
   lfsd::NormalMatrixArgs<double> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const double*)horizon,
-                                   (const double*)taus, (const double*)auxX_grid, (double*)H};
+                                   (const double*)taus, (const double*)auxX_grid, (double*)H, (const double*)wp_weight};
   return lfsd_detail::launch_normal_matrix_f64(a, stream);
+}
+
+LFSD_API int lfsd_normal_matrix(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                const int* iface_idx, const void* horizon, const void* taus, const void* auxX_grid, void* H,
+                                void* stream) {
+  return normal_matrix_dispatch(dtype, batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, horizon, taus, nullptr,
+                                auxX_grid, H, stream);
+}
+
+// (ABI 16) H = sum_k w_k J_k^T J_k; wp_weight == NULL: lfsd_normal_matrix
+LFSD_API int lfsd_normal_matrix_weighted(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                         const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
+                                         const void* auxX_grid, void* H, void* stream) {
+  return normal_matrix_dispatch(dtype, batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, horizon, taus, wp_weight,
+                                auxX_grid, H, stream);
 }
 
 LFSD_API int lfsd_lm_step(int dtype, int batch, int n_param, double lambda_down, double lambda_up, double lambda_min,

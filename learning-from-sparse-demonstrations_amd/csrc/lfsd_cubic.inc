@@ -1,6 +1,6 @@
 // Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
 // the sampling kernels (ABI 12: cpdp_sample.h), the per-row rules (ABI 13: cpdp_opt.h) and the Levenberg-Marquardt kernels (ABI 14:
-// cpdp_lm.h) and the per-group reduction (ABI 15: cpdp_groups.h).  They live
+// cpdp_lm.h), the per-group reduction (ABI 15: cpdp_groups.h) and the weighted forward sweeps (ABI 16).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -21,6 +21,27 @@ int launch_forward_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCub
 int launch_forward_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a) {
   LFSD_LAUNCH((lfsd::aux_forward_cubic_kernel<Model, double, GF_CUBIC>), grid, 64, stream, a);
   return launch_status();
+}
+// ---- ABI 16: the forward sweeps with a weight per waypoint, both levels (kernels of their own: cpdp_aux.h) ----
+template <typename T> static int launch_forward_weighted(unsigned grid, void* stream, const lfsd::AuxArgsCubic<T>& a, bool cubic, const T* wp_weight) {
+  if (cubic) {
+    lfsd::AuxArgsCubicWeighted<T> w;
+    static_cast<lfsd::AuxArgsCubic<T>&>(w) = a;
+    w.wp_weight = wp_weight;
+    LFSD_LAUNCH((lfsd::aux_forward_cubic_weighted_kernel<Model, T, GF_CUBIC>), grid, 64, stream, w);
+  } else {
+    lfsd::AuxArgsWeighted<T> w;
+    static_cast<lfsd::AuxArgs<T>&>(w) = a;
+    w.wp_weight = wp_weight;
+    LFSD_LAUNCH((lfsd::aux_forward_weighted_kernel<Model, T, GF_CUBIC>), grid, 64, stream, w);
+  }
+  return launch_status();
+}
+int launch_forward_weighted_f32(unsigned grid, void* stream, const lfsd::AuxArgsCubic<float>& a, bool cubic, const float* wp_weight) {
+  return launch_forward_weighted<float>(grid, stream, a, cubic, wp_weight);
+}
+int launch_forward_weighted_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a, bool cubic, const double* wp_weight) {
+  return launch_forward_weighted<double>(grid, stream, a, cubic, wp_weight);
 }
 // The emulator runs every lane as a fiber with a stack of its own: its launches stay small.
 #if defined(LFSD_EMU)

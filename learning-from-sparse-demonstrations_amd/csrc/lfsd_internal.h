@@ -69,6 +69,9 @@ int launch_riccati_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCub
 int launch_riccati_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a);
 int launch_forward_cubic_f32(unsigned grid, void* stream, const lfsd::AuxArgsCubic<float>& a);
 int launch_forward_cubic_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a);
+// the forward sweeps with a weight per waypoint (ABI 16; `cubic`: along the cubic interpolant, else `a` is read as its AuxArgs base)
+int launch_forward_weighted_f32(unsigned grid, void* stream, const lfsd::AuxArgsCubic<float>& a, bool cubic, const float* wp_weight);
+int launch_forward_weighted_f64(unsigned grid, void* stream, const lfsd::AuxArgsCubic<double>& a, bool cubic, const double* wp_weight);
 int launch_grid_curvature_f32(int batch, int n_grid, int n_comp, const float* grid, float* curv, void* stream);
 int launch_grid_curvature_f64(int batch, int n_grid, int n_comp, const double* grid, double* curv, void* stream);
 // sampling the interpolants / chain rule of a user-written loss (ABI 12, cpdp_sample.h; the same third unit)

@@ -283,7 +283,7 @@ class ModelLibrary:
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
                "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
                "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step",
-               "lfsd_group_reduce")
+               "lfsd_group_reduce", "lfsd_aux_forward_weighted", "lfsd_aux_forward_cubic_weighted", "lfsd_normal_matrix_weighted")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -323,13 +323,19 @@ class ModelLibrary:
         L.lfsd_trace_append.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_normal_matrix.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_lm_step.argtypes = [ci, ci, ci, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # (ABI 16: wp_weight after waypoints / after taus)
+        L.lfsd_aux_forward_weighted.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                ci, cd, vp, vp, ci, vp]
+        L.lfsd_aux_forward_cubic_weighted.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp,
+                                                      vp, vp, ci, cd, vp, vp, ci, vp]
+        L.lfsd_normal_matrix_weighted.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_group_reduce.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 15:
+        if rc != 0 or info.abi_version != 16:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -534,8 +540,12 @@ class ModelLibrary:
 
     def aux_solve(self, horizon, auxvar, consts, state_grid, control_grid, costate_grid, taus, waypoints, iface_idx,
                   substeps=0, want_grids=False, Z_grid=None, out=None, phase_hook=None, rtol=1e-3, oc_status=None,
-                  skip_status=(), interp_level=1, curvature=None):
-        """``interp_level`` 1: the sweeps differentiate along the linear interpolant of the grids (CPDP.py:386); 2: along their cubic
+                  skip_status=(), interp_level=1, curvature=None, wp_weight=None):
+        """``wp_weight`` [B, K] or None (include/lfsd_cpdp.h, ABI 16): a weight per waypoint, loss = sum_k w_k |r_k|^2; a zero weight
+        removes the waypoint (its tau and target are not read); non-negative and finite, which the caller guarantees (nothing is
+        read back here).  With weights the call is ``lfsd_aux_riccati`` then ``lfsd_aux_forward_weighted`` (there is no weighted
+        ``lfsd_aux_solve``); None: the launches as ever.
+        ``interp_level`` 1: the sweeps differentiate along the linear interpolant of the grids (CPDP.py:386); 2: along their cubic
         interpolant (CPDP.py:388-390; the ``*_cubic`` entry points).  ``curvature``: at level 2, the (state, control, costate)
         curvature tensors if the caller has them (``grid_curvature``); fitted here otherwise; returned as ``out["curvature"]``.
         ``phase_hook(name)``, if given, is called before/after each of the two launches
@@ -573,6 +583,9 @@ class ModelLibrary:
             self._check(taus, (B, nw), dt, "taus")
             self._check(waypoints, (B, nw, ni), dt, "waypoints")
             self._check(iface_idx, (ni,), torch.int32, "iface_idx", optional=True)
+            self._check(wp_weight, (B, nw), dt, "wp_weight", optional=True)
+        elif wp_weight is not None:
+            raise LfsdError("wp_weight without waypoints")
         if Z_grid is None:
             Z_grid = torch.empty((B, N + 1, n + p, n), dtype=dt, device=dev)
         if out is None:
@@ -614,6 +627,12 @@ class ModelLibrary:
         tail = (nw, ni, self._p(iface_idx), self._p(taus), self._p(waypoints), self._p(out["loss"]),
                 self._p(out["grad"]), self._p(auxX), self._p(auxU), int(substeps), float(rtol), self._p(out["stats"]),
                 self._p(oc_status), skip_mask, self._stream(state_grid))
+        fwd = "lfsd_aux_forward" + sfx
+        if wp_weight is not None:      # the weighted forward sweep: wp_weight goes after waypoints
+            fwd += "_weighted"
+            tail = tail[:5] + (self._p(wp_weight),) + tail[5:]
+            if phase_hook is None:
+                phase_hook = lambda name: None
         with self._on(state_grid):
             if phase_hook is None:
                 self._rc(getattr(self.lib, "lfsd_aux_solve" + sfx)(*common, *tail), "lfsd_aux_solve" + sfx)
@@ -623,7 +642,7 @@ class ModelLibrary:
                                                                      self._p(oc_status), skip_mask, self._stream(state_grid)),
                          "lfsd_aux_riccati" + sfx)
                 phase_hook("forward")
-                self._rc(getattr(self.lib, "lfsd_aux_forward" + sfx)(*common, *tail), "lfsd_aux_forward" + sfx)
+                self._rc(getattr(self.lib, fwd)(*common, *tail), fwd)
                 phase_hook("end")
         out["Z_grid"] = Z_grid
         out["auxX_grid"], out["auxU_grid"] = auxX, auxU
@@ -730,8 +749,10 @@ class ModelLibrary:
         self._rc(rc, "lfsd_trace_append")
 
     # ---- ABI 14: Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step --------------------------------------------
-    def normal_matrix(self, horizon, taus, auxX_grid, iface_idx, out=None):
-        """H [B, p, p] = J^T J of the waypoint residuals (include/lfsd_cpdp.h, ABI 14): J is the linear interpolant of ``auxX_grid``
+    def normal_matrix(self, horizon, taus, auxX_grid, iface_idx, out=None, wp_weight=None):
+        """``wp_weight`` [B, K] or None (ABI 16): H = sum_k w_k J_k^T J_k through ``lfsd_normal_matrix_weighted``; a zero weight removes
+        the waypoint; None: ``lfsd_normal_matrix`` as ever.
+        H [B, p, p] = J^T J of the waypoint residuals (include/lfsd_cpdp.h, ABI 14): J is the linear interpolant of ``auxX_grid``
         [B, n_grid+1, p, n] at ``taus`` [B, K], restricted to the state components ``iface_idx`` [n_iface] int32.  horizon [B].
         Exactly symmetric; fixed summation order: a row's H is the same bits in any batch.  An entry of ``iface_idx`` outside
         [0, n) is found on the device (nothing is read back here): the call then writes nothing.  Small eigenvalues of H are
@@ -756,10 +777,16 @@ class ModelLibrary:
         if out is None:
             out = torch.empty((B, p, p), dtype=dt, device=auxX_grid.device)
         self._check(out, (B, p, p), dt, "out")
+        self._check(wp_weight, (B, K), dt, "wp_weight", optional=True)
         with self._on(auxX_grid):
-            rc = self.lib.lfsd_normal_matrix(_DT[dt], B, N1 - 1, n, p, K, ni, self._p(iface_idx), self._p(horizon), self._p(taus),
-                                             self._p(auxX_grid), self._p(out), self._stream(auxX_grid))
-        self._rc(rc, "lfsd_normal_matrix")
+            if wp_weight is None:
+                rc = self.lib.lfsd_normal_matrix(_DT[dt], B, N1 - 1, n, p, K, ni, self._p(iface_idx), self._p(horizon), self._p(taus),
+                                                 self._p(auxX_grid), self._p(out), self._stream(auxX_grid))
+            else:
+                rc = self.lib.lfsd_normal_matrix_weighted(_DT[dt], B, N1 - 1, n, p, K, ni, self._p(iface_idx), self._p(horizon),
+                                                          self._p(taus), self._p(wp_weight), self._p(auxX_grid), self._p(out),
+                                                          self._stream(auxX_grid))
+        self._rc(rc, "lfsd_normal_matrix" if wp_weight is None else "lfsd_normal_matrix_weighted")
         return out
 
     def lm_step(self, theta, loss_acc, grad_acc, H_acc, lam, theta_trial, loss_t, grad_t, H_t, lambda_down=1.0 / 3.0, lambda_up=2.0,
