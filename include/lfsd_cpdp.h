@@ -35,6 +35,9 @@
  *   lfsd_aux_forward_weighted / lfsd_aux_forward_cubic_weighted / lfsd_normal_matrix_weighted   a weight per waypoint in the loss of
  *                         lib/QuadAlgorithm.py:616-639 (the reference weighs every waypoint equally); with zero weights, demonstrations
  *                         of different lengths in one batch, as Examples/quad_example_human_input.py collects them (ABI 16)
+ *   lfsd_waypoint_time_grad / lfsd_tau_project   no counterpart: the reference invents the waypoint times (lib/InputWaypoints.py:212-228,
+ *                         generate_time: chord length over an average speed) and then treats them as exact in the loss of
+ *                         lib/QuadAlgorithm.py:616-673; the derivative of that loss in the times, and their ordered update (ABI 17)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -43,7 +46,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 16
+#define LFSD_ABI_VERSION 17
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -419,6 +422,51 @@ int lfsd_aux_forward_cubic_weighted(int dtype, int batch, int n_grid,
 int lfsd_normal_matrix_weighted(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
                                 const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
                                 const void* auxX_grid, void* H, void* stream);
+
+/* ABI 17 -- learnable waypoint times.  The times tau_k of a sparse demonstration are guesses: the reference's human-input path builds
+ * them from chord length divided by an average speed, rounded to 0.01 s (lib/InputWaypoints.py:212-228), and the loss of
+ * lib/QuadAlgorithm.py:616-673 then takes them as exact.  The time-warp parameter stretches the whole axis by one factor; it cannot
+ * repair times that are wrong by different amounts.  lfsd_waypoint_time_grad is the derivative of the fused loss in the times:
+ *   dtau[b][k] = w_k r^T (dy/dx)(x(tau_k)) xdot(tau_k) + tau_prior (tau_k - tau_ref[b][k]),      r = y(x(tau_k)) - waypoints[b][k]
+ * with NO factor 2 (the convention of the fused gradient: d loss / d tau_k = 2 dtau with tau_prior = 0).  x(t) is the interpolant of
+ * state_grid [B][n_grid+1][n_state] -- linear (curv == NULL), or the cubic of lfsd_sample_grid with curv = lfsd_grid_curvature of the
+ * state grid (n_grid >= 3) -- interval and fraction as in lfsd_sample_grid (a tau on a node belongs to the interval on its right,
+ * tau = horizon is interval n_grid-1 at s = 1), and xdot the derivative in t of that very expression:
+ *   (x_k+1 - x_k) / h   [ + ((1 - 3 (1-s)^2) c_k + (3 s^2 - 1) c_k+1) / h ].
+ * iface_idx [n_iface] int32 picks state components; NULL selects the interface function compiled into the library (n_iface =
+ * lfsd_interface_dim()), evaluated as the fused loss evaluates it, with the constants `consts` [B][n_const] (const_per_traj = 1) or
+ * [n_const] (0) it may depend on (the consts of lfsd_aux_forward; never read with an index list, NULL is fine there).  This is why the
+ * call lives in the model library.  horizon [B]; taus, dtau, wp_weight, tau_ref [B][n_waypoints]; waypoints [B][n_waypoints][n_iface].
+ * wp_weight NULL: weight 1.  A weight of exactly 0 means the waypoint does not exist: dtau = +0.0 and its tau, target and tau_ref are
+ * never read (NaN padding is fine).  The other weights enter through the scaled residual w r, formed once: all-ones weights give the
+ * bits of NULL, powers of two scale dtau exactly.  tau_ref NULL or tau_prior == 0: no prior term.
+ * One thread per (trajectory, waypoint) sums the components in ascending order; no atomics: a row's dtau is the same bits in any
+ * batch.  A NaN row of state_grid gives a NaN row of dtau and touches no other.  An entry of iface_idx outside [0, n_state) is found
+ * ON THE DEVICE, as lfsd_normal_matrix finds it: the call returns 0 and writes no word of dtau.
+ * LFSD_EINVAL, before any launch: batch / n_waypoints / n_iface <= 0, n_grid < 1 (< 3 with curv), an unknown dtype, a NULL state_grid /
+ * horizon / taus / waypoints / dtau, iface_idx NULL in a library without a compiled interface, with another n_iface, or without the
+ * consts that library needs, tau_prior negative or not finite (also after the cast to `dtype`), dtau overlapping an input, more than
+ * 2^31-1 workgroups. */
+int lfsd_waypoint_time_grad(int dtype, int batch, int n_grid, int n_waypoints, int n_iface,
+                            const void* state_grid, const void* curv, const void* horizon,
+                            const void* consts, int const_per_traj,
+                            const void* taus, const void* waypoints, const int* iface_idx,
+                            const void* wp_weight, const void* tau_ref, double tau_prior, void* dtau, void* stream);
+
+/* The projection of an updated (or looked-ahead) time vector: it keeps the existing waypoints of a row strictly ordered and inside
+ * (0, horizon).  tau_ref [B][n_waypoints]: ordered times, typically those the step started from; tau_io [B][n_waypoints]: in the
+ * proposal, out the projected times.  For every existing waypoint k (wp_weight NULL or wp_weight[b][k] != 0), with prev / next the
+ * nearest existing waypoints on either side in tau_ref (0 before the first, horizon[b] after the last) and c = max_shift:
+ *   tau_io[k] <- clamp(clamp(tau_io[k], tau_lo[b][k], tau_hi[b][k]),  ref_k - c (ref_k - ref_prev),  ref_k + c (ref_next - ref_k)).
+ * With 0 < c < 0.5 the gap of two neighbours stays at least (1 - 2c) of what it was, whatever the update rule proposed.  The window
+ * is applied last: where tau_lo / tau_hi (either may be NULL) do not intersect it, the order wins.  A proposal that is not finite
+ * keeps ref_k.  Rows with row_active[b] == 0 and waypoints that do not exist keep tau_io bit for bit (and nothing of such a waypoint
+ * is read).  One thread per row; every clamp reads tau_ref only.
+ * LFSD_EINVAL, before any launch: batch or n_waypoints <= 0, an unknown dtype, a NULL tau_ref / tau_io / horizon, max_shift outside
+ * (0, 0.5) as a double or after the cast to `dtype` (a NaN included), tau_io overlapping another array. */
+int lfsd_tau_project(int dtype, int batch, int n_waypoints, const void* tau_ref, void* tau_io, const void* horizon,
+                     const void* wp_weight, const void* tau_lo, const void* tau_hi, double max_shift,
+                     const int* row_active, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

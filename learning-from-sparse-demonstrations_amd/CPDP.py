@@ -656,6 +656,24 @@ def pad_demonstrations(taus_list, waypoints_list, weights_list=None):
     return taus, wps, wts
 
 
+def chord_length_times(points, average_speed):
+    """Time stamps for a polyline flown at a constant speed, as the reference's human-input path invents them
+    (lib/InputWaypoints.py:212-228, ``generate_time``): ``points`` [P, d] are the start, the waypoints and the goal; every segment
+    takes its chord length divided by ``average_speed``, rounded to 0.01, and the stamps are the running sum from 0.  Returns [P]
+    float64: ``[0]`` is 0, ``[1:-1]`` are the waypoint times, ``[-1]`` is the horizon.  Such times are guesses: what
+    ``SparseDemoLearner(learn_taus=True)`` corrects."""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[0] < 2:
+        raise LfsdError("points is [P, d] with P >= 2: start, waypoints, goal (got shape %s)" % (pts.shape,))
+    speed = float(average_speed)
+    if not (np.isfinite(speed) and speed > 0):
+        raise LfsdError("average_speed must be positive and finite (got %r)" % (average_speed,))
+    out = np.zeros(pts.shape[0], dtype=np.float64)
+    for i in range(1, pts.shape[0]):
+        out[i] = round(float(np.linalg.norm(pts[i] - pts[i - 1])) / speed, 2) + out[i - 1]
+    return out
+
+
 class SparseDemoLearner:
     """The outer learning iteration of the examples, batched on the device.
 
@@ -786,6 +804,30 @@ class SparseDemoLearner:
     second evaluation uses the same weights) and ``stop_rule`` (the weights move to the dense batch with ``taus`` and ``waypoints``).
     Refused with ``LfsdError``: together with ``loss_fn`` (a user loss does its own weighting), both arguments at once, negative or
     non-finite weights, a shape that is none of the above, a count outside [0, K].
+
+    ``learn_taus`` (default ``False`` = the times are data, the launches, buffers and bits the learner always had): the waypoint times
+    are learned beside theta.  They are guesses in the reference too -- its human-input path builds them from chord length over an
+    average speed (lib/InputWaypoints.py:212-228, ``chord_length_times``) -- and the time-warp parameter can only stretch them all by
+    one factor.  Every row owns its times [B, K] in all three modes (in shared and grouped mode each demonstration row keeps its own;
+    nothing about them is reduced or all-reduced).  One step: the evaluation at (theta point, tau point) through the unchanged fused
+    path; ``lfsd_waypoint_time_grad`` on the solved state grid (at level 2 with its curvature grid) gives
+    ``tau_grad[b, k] = w_k r^T dy/dx xdot(tau_k) + tau_prior (tau_k - tau0[b, k])``, no factor 2, as the fused gradient; the theta
+    update as ever; ``lfsd_optimizer_step`` on ``taus`` with moments of their own (``m_tau``, ``v_tau``, ``vhat_tau``) under
+    ``tau_method`` (default: ``method``, or "Vanilla" when that is a per-row list; momentum and Adam constants are the learner's
+    scalars) at ``tau_learning_rate`` (required: times and parameters have different units); ``lfsd_tau_project`` against the times
+    the step started from: a time moves by at most ``tau_max_shift`` (in (0, 0.5), default 0.25) of the gap to its neighbour (0 and
+    the horizon at the ends) per step, after ``tau_bounds = (lo, hi)`` ([K] or [B, K]), so the existing waypoints of a row stay
+    strictly ordered inside the horizon whatever the rule proposed.  Under "Nesterov" the tau point is the look-ahead
+    ``taus + mu m_tau`` passed through the same projection against ``taus``.  A row frozen for the step (``skip_unconverged``) keeps
+    its times and their moments bit for bit.  The clamp does NOT correct the moments when it binds: a velocity or first moment keeps
+    pushing against the window until the gradient turns.  ``taus`` are the current times, ``tau_grad`` the last gradient, ``tau0``
+    the demonstrated times (also the reference of the prior); ``step()`` keeps returning (loss, grad).  It combines with the five
+    rules and per-row rule lists, ``interplation_level=2``, ``waypoint_weights`` / ``n_waypoints`` / ``pad_demonstrations`` (an absent
+    waypoint has gradient +0 and is never read or moved), ``warm_start``, ``skip_unconverged``, ``trace`` and
+    ``true_loss_print_flag`` (the second evaluation runs at ``taus``).  Refused with ``LfsdError``: ``loss_fn``, ``method="LM"`` (the
+    joint Gauss-Newton step needs the tau columns eliminated per waypoint), ``stop_rule`` (its gather of ``taus`` runs only when the
+    set shrinks), initial times that are not strictly increasing inside [0, horizon] among the existing waypoints, and
+    ``tau_learning_rate=None``.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
@@ -793,8 +835,24 @@ class SparseDemoLearner:
                  mode="independent", process_group=None, true_loss_print_flag=False, warm_start=False,
                  skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None,
                  lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8, demos_per_seed=None,
-                 waypoint_weights=None, n_waypoints=None):
+                 waypoint_weights=None, n_waypoints=None, learn_taus=False, tau_learning_rate=None, tau_method=None,
+                 tau_max_shift=0.25, tau_bounds=None, tau_prior=0.0):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
+        self._tau = None              # state of the learnable waypoint times (learn_taus), None: the times are data
+        self._tau_pt = None           # the times the next evaluation runs at when they differ from `taus` (the look-ahead point)
+        self.tau_grad = None
+        if learn_taus:
+            if loss_fn is not None:
+                raise LfsdError("learn_taus differentiates the fused waypoint loss in its times: a loss_fn samples taus on its own")
+            if method == "LM":
+                raise LfsdError("learn_taus with method='LM': the joint Gauss-Newton step needs the tau columns eliminated per "
+                                "waypoint (a follow-up, DESIGN.md section 17); use one of the five first-order rules")
+            if stop_rule is not None:
+                raise LfsdError("learn_taus does not combine with stop_rule yet: the dense batch gathers taus only when the set of "
+                                "seeds shrinks, moving times would need it every step")
+            if tau_learning_rate is None:
+                raise LfsdError("learn_taus=True needs tau_learning_rate: times and parameters have different units, there is no "
+                                "default step")
         if waypoint_weights is not None and n_waypoints is not None:
             raise LfsdError("waypoint_weights and n_waypoints are two spellings of one array (n_waypoints: weight 1 below the count, 0 "
                             "from it on): give one")
@@ -912,6 +970,9 @@ class SparseDemoLearner:
                             accepted=torch.zeros(R, dtype=torch.int32, device=dev))
             self._H_t = self._H_full = None
         self._init_trace(trace)
+        self.tau0 = self.taus
+        if learn_taus:
+            self._init_taus(tau_learning_rate, tau_method, tau_max_shift, tau_bounds, tau_prior)
         # warm_start: start every OC solve from the previous iteration's controls (theta moves little per step).
         # The reference cold-starts IPOPT every time; the converged KKT point is the same, only the path to it is shorter.
         self.warm_start = warm_start
@@ -987,6 +1048,99 @@ class SparseDemoLearner:
     def _wkw(self, wts):
         """The keyword that carries the weights into auxSysSolverBatch; without weights the call is what it always was."""
         return {} if wts is None else dict(waypoint_weights=wts)
+
+    # ---- learnable waypoint times (ABI 17) ---------------------------------------------------------------------------------
+    def _init_taus(self, lr, method, max_shift, bounds, prior):
+        """State of ``learn_taus``: the times become a [B, K] array of their own with optimizer moments, checked once, here."""
+        B, K = self.taus.shape
+        dt, dev = self.taus.dtype, self.taus.device
+        if method is None:
+            method = self.method if isinstance(self.method, str) else "Vanilla"
+        if not isinstance(method, str) or method not in runtime.OPT_METHODS or method == "LM":
+            raise LfsdError("tau_method is one of the five first-order rules (got %r)" % (method,))
+        lr, c, prior = float(lr), float(max_shift), float(prior)
+        if not (np.isfinite(lr) and lr >= 0):
+            raise LfsdError("tau_learning_rate must be finite and non-negative (got %r)" % (lr,))
+        if not 0 < c < 0.5:
+            raise LfsdError("tau_max_shift must lie in (0, 0.5): a time moves by at most that fraction of the gap to its neighbour "
+                            "per step, so the order cannot invert (got %r)" % (c,))
+        if not (np.isfinite(prior) and prior >= 0):
+            raise LfsdError("tau_prior must be finite and non-negative (got %r)" % (prior,))
+        # the initial times: strictly increasing inside [0, horizon] among the waypoints that exist (one host read, at set-up)
+        t = self.taus.detach().double().cpu().numpy()
+        hz = self.hz.detach().double().cpu().numpy()
+        w = None if self.wts is None else self.wts.detach().cpu().numpy()
+        for b in range(B):
+            tb = t[b] if w is None else t[b][w[b] != 0]
+            if tb.size and not (np.all(np.isfinite(tb)) and tb[0] >= 0 and tb[-1] <= hz[b] and np.all(np.diff(tb) > 0)):
+                raise LfsdError("learn_taus needs initial taus strictly increasing inside [0, horizon] among the existing waypoints "
+                                "(row %d: %s, horizon %g)" % (b, tb.tolist(), hz[b]))
+        lo = hi = None
+        if bounds is not None:
+            if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+                raise LfsdError("tau_bounds is (lo, hi), each [K] or [B, K]")
+            both = []
+            for nm, x in zip(("lo", "hi"), bounds):
+                x = x.detach().double().cpu() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+                if x.dim() == 1 and x.shape[0] == K:
+                    x = x.unsqueeze(0).expand(B, K)
+                elif tuple(x.shape) != (B, K):
+                    raise LfsdError("tau_bounds %s has shape %s: [K] or [B, K] = %s" % (nm, tuple(x.shape), (B, K)))
+                if bool(torch.isnan(x).any()):
+                    raise LfsdError("tau_bounds %s holds a NaN" % nm)
+                both.append(x.to(device=dev, dtype=dt).contiguous())
+            lo, hi = both
+        self.tau0 = self.taus.clone()         # the demonstrated times: tau_ref of the prior
+        self.taus = self.taus.clone()         # (the learner's own array: the caller's tensor is never written)
+        z = lambda: torch.zeros((B, K), dtype=dt, device=dev)
+        # (the rule's other hyper-parameters are the learner's; where those are given per row, the defaults)
+        sc = lambda x, dflt: dflt if self._per_row(x) is not None else float(x)
+        self._tau = dict(method=method, lr=lr, c=c, prior=prior, lo=lo, hi=hi, m=z(), v=z(), vhat=z(), start=z(),
+                         mu=sc(self.mu, 0.9), b1=sc(self.b1, 0.9), b2=sc(self.b2, 0.999), eps=sc(self.eps, 1e-8))
+        self.tau_grad = z()
+
+    m_tau = property(lambda self: None if self._tau is None else self._tau["m"], doc="[B, K] first moment / velocity of the times")
+    v_tau = property(lambda self: None if self._tau is None else self._tau["v"], doc="[B, K] second moment of the times")
+    vhat_tau = property(lambda self: None if self._tau is None else self._tau["vhat"], doc="[B, K] AMSGrad maximum of the times")
+
+    def _tau_eval_point(self):
+        """The times the step evaluates at: ``taus``, or under Nesterov the look-ahead ``taus + mu m_tau`` (the velocity is the
+        array lfsd_optimizer_step keeps it in) passed through lfsd_tau_project against ``taus``, so it is ordered too."""
+        s = self._tau
+        if s["method"] != "Nesterov":
+            return None
+        look = self.lib.lookahead(self.taus, s["m"], s["mu"])
+        return self.lib.tau_project(self.taus, look, self.hz, s["c"], wp_weight=self.wts, tau_lo=s["lo"], tau_hi=s["hi"])
+
+    def _tau_gradient(self):
+        """dLoss/dtau (no factor 2) of the evaluation just made, from its solved state grid: one launch (lfsd_waypoint_time_grad)."""
+        s, sol, aux = self._tau, self._sol, self._aux
+        if self.event_hook is not None:
+            self.event_hook("tau_grad")
+        ad = aux["loss"].dtype                        # (the sweeps' arithmetic: at level 2 the curvature grid is in it)
+        cv = lambda t: None if t is None else t.to(ad).contiguous()
+        curv = aux["curvature"][0] if aux.get("curvature") is not None else None
+        taus = self.taus if self._tau_pt is None else self._tau_pt
+        consts = None
+        if self.iface is None:
+            consts = cv(sol["consts"])
+        g = self.lib.waypoint_time_grad(cv(sol["state_grid"]), cv(self.hz), cv(taus), cv(self.wps), self.iface, curv=curv,
+                                        consts=consts, wp_weight=cv(self.wts), tau_ref=cv(self.tau0) if s["prior"] > 0 else None,
+                                        tau_prior=s["prior"], out=self.tau_grad if ad == self.tau_grad.dtype else None)
+        self.tau_grad = g.to(self.taus.dtype)
+        return self.tau_grad
+
+    def _tau_update(self, dtau, row_active, iter_idx):
+        """The update of the times: lfsd_optimizer_step on ``taus`` and its own moments (p = K, no projection), then
+        lfsd_tau_project against the times the step started from.  Rows with row_active == 0 keep times and moments bit for bit."""
+        s = self._tau
+        if self.event_hook is not None:
+            self.event_hook("tau_update")
+        s["start"].copy_(self.taus)
+        self.lib.optimizer_step(s["method"], self.taus, dtau, iter_idx, s["lr"], s["mu"], s["b1"], s["b2"], s["eps"],
+                                m=s["m"], v=s["v"], vhat=s["vhat"], proj_lo=None, row_active=row_active)
+        self.lib.tau_project(s["start"], self.taus, self.hz, s["c"], wp_weight=self.wts, tau_lo=s["lo"], tau_hi=s["hi"],
+                             row_active=row_active)
 
     # ---- per-row update rules (hyper-parameter sweeps in one batch) and device traces -------------------------------------
     @staticmethod
@@ -1164,7 +1318,8 @@ class SparseDemoLearner:
         # a learner that freezes unconverged rows anyway does not pay for differentiating them (they are masked by their
         # status below): the diverged seeds of a fixed learning rate otherwise hold the Riccati launch 20x longer
         lm = self._lm is not None                        # (LM: the sensitivity grids are written too, J^T J is formed from them)
-        self._aux = self.oc.auxSysSolverBatch(self._sol, self.taus, self.wps, self.iface, want_grids=lm, Z_grid=self._Z,
+        taus = self.taus if self._tau_pt is None else self._tau_pt      # (learn_taus under Nesterov: the projected look-ahead times)
+        self._aux = self.oc.auxSysSolverBatch(self._sol, taus, self.wps, self.iface, want_grids=lm, Z_grid=self._Z,
                                               out=self._aux_out(), phase_hook=phase, validate=False,
                                               skip_status=(3, 4) if self.skip_unconverged else None,
                                               interplation_level=self.interplation_level, **self._wkw(self.wts))
@@ -1440,7 +1595,12 @@ class SparseDemoLearner:
         """step() of mode='grouped': evaluation point on G rows, evaluation and reduction (above), update on G rows."""
         self._check_trace_room()
         theta_eval = self._eval_point()
+        if self._tau is not None:
+            self._tau_pt = self._tau_eval_point()
         loss, grad = self._evaluate_grouped(theta_eval)
+        if self._tau is not None:
+            dtau = self._tau_gradient()
+            self._tau_pt = None
         hook = self.event_hook
         if hook is not None:
             hook("update")
@@ -1450,6 +1610,8 @@ class SparseDemoLearner:
             if self.count_unconverged:
                 self.n_unconverged = int(self.B - self.n_ok.sum().item())
         self._update(grad, row_active, loss)
+        if self._tau is not None:      # (every demonstration row owns its times: the mask is the rows', not the groups')
+            self._tau_update(dtau, None if self._ok is None else self._ok.to(torch.int32), self.iter_idx)
         self.iter_idx += 1
         if hook is not None:
             hook("end")
@@ -1475,7 +1637,12 @@ class SparseDemoLearner:
         self._check_trace_room()
         theta_eval = self._eval_point()
         self._ok = None
+        if self._tau is not None:
+            self._tau_pt = self._tau_eval_point()
         loss, grad = self.evaluate(theta_eval)
+        if self._tau is not None:
+            dtau = self._tau_gradient()
+            self._tau_pt = None
         hook = self.event_hook
         if hook is not None:
             hook("update")
@@ -1499,6 +1666,8 @@ class SparseDemoLearner:
                 if self.count_unconverged:
                     self.n_unconverged = int(self.B - self._ok.sum().item())
         self._update(grad_used, row_active, loss_out)
+        if self._tau is not None:      # (the times are per row in every mode: in shared mode a frozen demonstration keeps its own)
+            self._tau_update(dtau, row_active if self.mode != "shared" or self._ok is None else self._ok.to(torch.int32), self.iter_idx)
         self.iter_idx += 1
         if hook is not None:
             hook("end")

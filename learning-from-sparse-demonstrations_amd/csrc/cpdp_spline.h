@@ -18,6 +18,9 @@ namespace lfsd {
 // weights of c_k and c_k+1 at fraction s of an interval
 template <typename T> LFSD_DEV T cubic_wa(T s) { const T r = T(1) - s; return r * r * r - r; }
 template <typename T> LFSD_DEV T cubic_wb(T s) { return s * s * s - s; }
+// their derivatives in s (the slope of the interpolant, cpdp_times.h: divided by h they are derivatives in time)
+template <typename T> LFSD_DEV T cubic_dwa(T s) { const T r = T(1) - s; return T(1) - T(3) * r * r; }
+template <typename T> LFSD_DEV T cubic_dwb(T s) { return T(3) * s * s - T(1); }
 
 struct SplinePivots {
   static constexpr int N = 24;

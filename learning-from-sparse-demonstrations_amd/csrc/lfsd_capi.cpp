@@ -827,3 +827,72 @@ LFSD_API int lfsd_group_reduce(int dtype, int n_groups, int group_size, int n_pa
                                   (double*)loss_g, (double*)grad_g, (double*)H_g, n_ok};
   return lfsd_detail::launch_group_reduce_f64(a, stream);
 }
+
+// ---- ABI 17: learnable waypoint times -- dLoss/dtau of the waypoint loss and the ordered update (cpdp_times.h) ----
+template <typename T>
+static int waypoint_time_grad_t(int batch, int n_grid, int n_waypoints, int n_iface, const void* state_grid, const void* curv,
+                                const void* horizon, const void* consts, int const_per_traj, const void* taus, const void* waypoints,
+                                const int* iface_idx, const void* wp_weight, const void* tau_ref, double tau_prior, void* dtau,
+                                void* stream) {
+  lfsd::TimeGradArgs<T> a;
+  a.batch = batch; a.n_grid = n_grid; a.n_waypoints = n_waypoints; a.n_iface = n_iface;
+  a.state_grid = (const T*)state_grid; a.curv = (const T*)curv; a.horizon = (const T*)horizon;
+  a.consts = consts ? (const T*)consts : (const T*)horizon;      // (a model without constants: a readable word, as aux_phase_t does)
+  a.const_stride = (consts && const_per_traj) ? Model::NC : 0;
+  a.taus = (const T*)taus; a.waypoints = (const T*)waypoints; a.iface_idx = iface_idx;
+  a.wp_weight = (const T*)wp_weight; a.tau_ref = (const T*)tau_ref; a.tau_prior = (T)tau_prior; a.dtau = (T*)dtau;
+  if constexpr (sizeof(T) == 4) return lfsd_detail::launch_waypoint_time_grad_f32(a, stream);
+  else return lfsd_detail::launch_waypoint_time_grad_f64(a, stream);
+}
+
+LFSD_API int lfsd_waypoint_time_grad(int dtype, int batch, int n_grid, int n_waypoints, int n_iface, const void* state_grid,
+                                     const void* curv, const void* horizon, const void* consts, int const_per_traj,
+                                     const void* taus, const void* waypoints, const int* iface_idx, const void* wp_weight,
+                                     const void* tau_ref, double tau_prior, void* dtau, void* stream) {
+  if (batch <= 0 || n_grid < 1 || n_waypoints <= 0 || n_iface <= 0) return LFSD_EINVAL;
+  if (curv && n_grid < 3) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  if (!state_grid || !horizon || !taus || !waypoints || !dtau) return LFSD_EINVAL;
+  // iface_idx == NULL selects the interface function compiled into the library: it must exist, n_iface must be its size, and the
+  // constants it may read must be there
+  if (!iface_idx && (Model::NIF == 0 || n_iface != Model::NIF || (Model::NC_REAL > 0 && !consts))) return LFSD_EINVAL;
+  if (!(tau_prior >= 0) || !(tau_prior <= 1.7e308)) return LFSD_EINVAL;      // (false for a NaN)
+  if (dtype == LFSD_F32 && !(tau_prior <= 3.0e38)) return LFSD_EINVAL;      // (compared as a double: no cast of a value float cannot hold)
+  if (((unsigned long long)batch * (unsigned long long)n_waypoints + 255ull) / 256ull > 0x7fffffffull) return LFSD_EINVAL;
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, K = (unsigned long long)n_waypoints;
+  const unsigned long long ob = B * K * es, gb = B * (unsigned long long)(n_grid + 1) * Model::NX * es;
+  if (spans_overlap(dtau, ob, state_grid, gb) || spans_overlap(dtau, ob, curv, gb) || spans_overlap(dtau, ob, horizon, B * es) ||
+      spans_overlap(dtau, ob, taus, ob) || spans_overlap(dtau, ob, waypoints, ob * (unsigned long long)n_iface) ||
+      spans_overlap(dtau, ob, iface_idx, (unsigned long long)n_iface * sizeof(int)) || spans_overlap(dtau, ob, wp_weight, ob) ||
+      spans_overlap(dtau, ob, tau_ref, ob) ||
+      spans_overlap(dtau, ob, consts, (const_per_traj ? B : 1ull) * (unsigned long long)Model::NC * es))
+    return LFSD_EINVAL;
+  if (dtype == LFSD_F32)
+    return waypoint_time_grad_t<float>(batch, n_grid, n_waypoints, n_iface, state_grid, curv, horizon, consts, const_per_traj, taus,
+                                       waypoints, iface_idx, wp_weight, tau_ref, tau_prior, dtau, stream);
+  return waypoint_time_grad_t<double>(batch, n_grid, n_waypoints, n_iface, state_grid, curv, horizon, consts, const_per_traj, taus,
+                                      waypoints, iface_idx, wp_weight, tau_ref, tau_prior, dtau, stream);
+}
+
+LFSD_API int lfsd_tau_project(int dtype, int batch, int n_waypoints, const void* tau_ref, void* tau_io, const void* horizon,
+                              const void* wp_weight, const void* tau_lo, const void* tau_hi, double max_shift,
+                              const int* row_active, void* stream) {
+  if (batch <= 0 || n_waypoints <= 0) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  if (!tau_ref || !tau_io || !horizon) return LFSD_EINVAL;
+  if (!(max_shift > 0 && max_shift < 0.5)) return LFSD_EINVAL;      // (false for a NaN)
+  if (dtype == LFSD_F32 && !((float)max_shift > 0 && (float)max_shift < 0.5f)) return LFSD_EINVAL;      // ... and after the cast
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, ob = B * (unsigned long long)n_waypoints * es;
+  if (spans_overlap(tau_io, ob, tau_ref, ob) || spans_overlap(tau_io, ob, horizon, B * es) || spans_overlap(tau_io, ob, wp_weight, ob) ||
+      spans_overlap(tau_io, ob, tau_lo, ob) || spans_overlap(tau_io, ob, tau_hi, ob) ||
+      spans_overlap(tau_io, ob, row_active, B * sizeof(int)))
+    return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::TauProjectArgs<float> a{batch, n_waypoints, (const float*)tau_ref, (float*)tau_io, (const float*)horizon,
+                                  (const float*)wp_weight, (const float*)tau_lo, (const float*)tau_hi, (float)max_shift, row_active};
+    return lfsd_detail::launch_tau_project_f32(a, stream);
+  }
+  lfsd::TauProjectArgs<double> a{batch, n_waypoints, (const double*)tau_ref, (double*)tau_io, (const double*)horizon,
+                                 (const double*)wp_weight, (const double*)tau_lo, (const double*)tau_hi, max_shift, row_active};
+  return lfsd_detail::launch_tau_project_f64(a, stream);
+}

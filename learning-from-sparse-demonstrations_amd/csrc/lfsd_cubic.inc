@@ -1,6 +1,7 @@
 // Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
 // the sampling kernels (ABI 12: cpdp_sample.h), the per-row rules (ABI 13: cpdp_opt.h) and the Levenberg-Marquardt kernels (ABI 14:
-// cpdp_lm.h), the per-group reduction (ABI 15: cpdp_groups.h) and the weighted forward sweeps (ABI 16).  They live
+// cpdp_lm.h), the per-group reduction (ABI 15: cpdp_groups.h), the weighted forward sweeps (ABI 16) and the kernels of the learnable waypoint
+// times (ABI 17: cpdp_times.h).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -150,4 +151,23 @@ template <typename T> static int launch_group_reduce(const lfsd::GroupReduceArgs
 }
 int launch_group_reduce_f32(const lfsd::GroupReduceArgs<float>& a, void* stream) { return launch_group_reduce<float>(a, stream); }
 int launch_group_reduce_f64(const lfsd::GroupReduceArgs<double>& a, void* stream) { return launch_group_reduce<double>(a, stream); }
+// ---- ABI 17: learnable waypoint times -- dLoss/dtau of the waypoint loss, the ordered update (cpdp_times.h) ----
+// one thread per (trajectory, waypoint); batch and n_waypoints are positive ints, so the thread count stays below 2^62
+template <typename T> static int launch_waypoint_time_grad(const lfsd::TimeGradArgs<T>& a, void* stream) {
+  unsigned grid;
+  if (!rows_grid(a.batch, a.n_waypoints, &grid)) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::waypoint_time_grad_kernel<Model, T>), grid, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_waypoint_time_grad_f32(const lfsd::TimeGradArgs<float>& a, void* stream) { return launch_waypoint_time_grad<float>(a, stream); }
+int launch_waypoint_time_grad_f64(const lfsd::TimeGradArgs<double>& a, void* stream) { return launch_waypoint_time_grad<double>(a, stream); }
+// one thread per row
+template <typename T> static int launch_tau_project(const lfsd::TauProjectArgs<T>& a, void* stream) {
+  unsigned grid;
+  if (!rows_grid(a.batch, 1, &grid)) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::tau_project_kernel<T>), grid, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_tau_project_f32(const lfsd::TauProjectArgs<float>& a, void* stream) { return launch_tau_project<float>(a, stream); }
+int launch_tau_project_f64(const lfsd::TauProjectArgs<double>& a, void* stream) { return launch_tau_project<double>(a, stream); }
 }

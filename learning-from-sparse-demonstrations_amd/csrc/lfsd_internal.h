@@ -94,4 +94,9 @@ int launch_lm_step_f64(const lfsd::LmStepArgs<double>& a, void* stream);
 // per-group sums of several demonstrations per seed (ABI 15, cpdp_groups.h; the same third unit)
 int launch_group_reduce_f32(const lfsd::GroupReduceArgs<float>& a, void* stream);
 int launch_group_reduce_f64(const lfsd::GroupReduceArgs<double>& a, void* stream);
+// learnable waypoint times (ABI 17, cpdp_times.h; the same third unit)
+int launch_waypoint_time_grad_f32(const lfsd::TimeGradArgs<float>& a, void* stream);
+int launch_waypoint_time_grad_f64(const lfsd::TimeGradArgs<double>& a, void* stream);
+int launch_tau_project_f32(const lfsd::TauProjectArgs<float>& a, void* stream);
+int launch_tau_project_f64(const lfsd::TauProjectArgs<double>& a, void* stream);
 }

@@ -106,7 +106,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_groups.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_groups.h", "cpdp_times.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
                   "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
@@ -283,7 +283,8 @@ class ModelLibrary:
                "lfsd_stop_compact", "lfsd_gather_rows", "lfsd_scatter_rows", "lfsd_grid_curvature", "lfsd_aux_solve_cubic",
                "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
                "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step",
-               "lfsd_group_reduce", "lfsd_aux_forward_weighted", "lfsd_aux_forward_cubic_weighted", "lfsd_normal_matrix_weighted")
+               "lfsd_group_reduce", "lfsd_aux_forward_weighted", "lfsd_aux_forward_cubic_weighted", "lfsd_normal_matrix_weighted",
+               "lfsd_waypoint_time_grad", "lfsd_tau_project")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -330,12 +331,15 @@ class ModelLibrary:
                                                       vp, vp, ci, cd, vp, vp, ci, vp]
         L.lfsd_normal_matrix_weighted.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_group_reduce.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # (ABI 17: learnable waypoint times)
+        L.lfsd_waypoint_time_grad.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, cd, vp, vp]
+        L.lfsd_tau_project.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, cd, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 16:
+        if rc != 0 or info.abi_version != 17:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -855,6 +859,86 @@ class ModelLibrary:
                                             self._p(loss_g), self._p(grad_g), self._p(H_g), self._p(n_ok), self._stream(grad))
         self._rc(rc, "lfsd_group_reduce")
         return loss_g, grad_g, H_g, n_ok
+
+    # ---- ABI 17: learnable waypoint times ---------------------------------------------------------------------------------------------
+    def waypoint_time_grad(self, state_grid, horizon, taus, waypoints, iface_idx, curv=None, consts=None, wp_weight=None,
+                           tau_ref=None, tau_prior=0.0, out=None):
+        """dtau [B, K] = w_k r^T dy/dx xdot(tau_k) + tau_prior (tau_k - tau_ref_k): half the derivative of the fused waypoint loss
+        in the waypoint times (include/lfsd_cpdp.h, ABI 17).  state_grid [B, n_grid+1, n], horizon [B], taus [B, K], waypoints
+        [B, K, n_iface]; ``iface_idx`` [n_iface] int32, or None for the interface compiled into the library (then ``consts`` as
+        aux_solve takes them); ``curv`` = ``grid_curvature(state_grid)`` for the cubic interpolant; ``wp_weight`` / ``tau_ref``
+        [B, K] or None.  A waypoint of weight 0 gets +0 and is never read.  Nothing is read back."""
+        if not isinstance(state_grid, torch.Tensor) or state_grid.dim() != 3 or state_grid.dtype not in _DT:
+            raise LfsdError("state_grid must be a [B, n_grid+1, n_state] float32 / float64 tensor")
+        dt = state_grid.dtype
+        B, N1, n = state_grid.shape
+        if n != self.n_state:
+            raise LfsdError("state_grid has %d state components, the model %d" % (n, self.n_state))
+        if N1 < 2 or (curv is not None and N1 < 4):
+            raise LfsdError("n_grid = %d: the linear interpolant needs two nodes, the cubic one four" % (N1 - 1))
+        if not isinstance(taus, torch.Tensor) or taus.dim() != 2 or taus.shape[1] < 1:
+            raise LfsdError("taus must be a [B, K] tensor with K >= 1")
+        K = taus.shape[1]
+        per_traj = 0
+        if iface_idx is None:
+            ni = self.n_interface
+            if ni == 0:
+                raise LfsdError("iface_idx=None selects the interface compiled into the library: this one has none")
+            if self.n_const:
+                if not isinstance(consts, torch.Tensor):
+                    raise LfsdError("consts is required by the compiled interface (n_const=%d)" % self.n_const)
+                per_traj = 1 if consts.dim() == 2 else 0
+                self._check(consts, (B, self.n_const) if per_traj else (self.n_const,), dt, "consts")
+            else:
+                consts = None
+        else:
+            if not isinstance(iface_idx, torch.Tensor) or iface_idx.dim() != 1 or iface_idx.shape[0] < 1:
+                raise LfsdError("iface_idx must be an int32 tensor of at least one state component")
+            ni = iface_idx.shape[0]
+            self._check(iface_idx, (ni,), torch.int32, "iface_idx")
+            consts = None
+        self._check(state_grid, (B, N1, n), dt, "state_grid")
+        self._check(curv, (B, N1, n), dt, "curv", optional=True)
+        self._check(horizon, (B,), dt, "horizon")
+        self._check(taus, (B, K), dt, "taus")
+        self._check(waypoints, (B, K, ni), dt, "waypoints")
+        self._check(wp_weight, (B, K), dt, "wp_weight", optional=True)
+        self._check(tau_ref, (B, K), dt, "tau_ref", optional=True)
+        if out is None:
+            out = torch.empty((B, K), dtype=dt, device=state_grid.device)
+        self._check(out, (B, K), dt, "out")
+        with self._on(state_grid):
+            rc = self.lib.lfsd_waypoint_time_grad(_DT[dt], B, N1 - 1, K, ni, self._p(state_grid), self._p(curv), self._p(horizon),
+                                                  self._p(consts), per_traj, self._p(taus), self._p(waypoints), self._p(iface_idx),
+                                                  self._p(wp_weight), self._p(tau_ref), float(tau_prior), self._p(out),
+                                                  self._stream(state_grid))
+        self._rc(rc, "lfsd_waypoint_time_grad")
+        return out
+
+    def tau_project(self, tau_ref, tau_io, horizon, max_shift, wp_weight=None, tau_lo=None, tau_hi=None, row_active=None):
+        """In place: ``tau_io`` [B, K] clamped to within ``max_shift`` (0 < c < 0.5) of the gap to the neighbours in the ordered
+        times ``tau_ref`` [B, K] (0 and horizon [B] at the ends), and to ``tau_lo`` / ``tau_hi`` [B, K] first (include/lfsd_cpdp.h,
+        ABI 17): the order of a row cannot invert.  Waypoints of weight 0 and rows with ``row_active`` == 0 keep their words; a
+        non-finite proposal keeps the reference time.  Returns ``tau_io``.  Nothing is read back."""
+        if not isinstance(tau_io, torch.Tensor) or tau_io.dim() != 2 or tau_io.dtype not in _DT or tau_io.shape[1] < 1:
+            raise LfsdError("tau_io must be a [B, K] float32 / float64 tensor with K >= 1")
+        dt = tau_io.dtype
+        B, K = tau_io.shape
+        self._check(tau_io, (B, K), dt, "tau_io")
+        self._check(tau_ref, (B, K), dt, "tau_ref")
+        self._check(horizon, (B,), dt, "horizon")
+        self._check(wp_weight, (B, K), dt, "wp_weight", optional=True)
+        self._check(tau_lo, (B, K), dt, "tau_lo", optional=True)
+        self._check(tau_hi, (B, K), dt, "tau_hi", optional=True)
+        self._check(row_active, (B,), torch.int32, "row_active", optional=True)
+        if tau_ref.data_ptr() == tau_io.data_ptr():
+            raise LfsdError("tau_project clamps tau_io against tau_ref: they are two arrays")
+        with self._on(tau_io):
+            rc = self.lib.lfsd_tau_project(_DT[dt], B, K, self._p(tau_ref), self._p(tau_io), self._p(horizon), self._p(wp_weight),
+                                           self._p(tau_lo), self._p(tau_hi), float(max_shift), self._p(row_active),
+                                           self._stream(tau_io))
+        self._rc(rc, "lfsd_tau_project")
+        return tau_io
 
     def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
                      eligible=None):
