@@ -38,6 +38,9 @@
  *   lfsd_waypoint_time_grad / lfsd_tau_project   no counterpart: the reference invents the waypoint times (lib/InputWaypoints.py:212-228,
  *                         generate_time: chord length over an average speed) and then treats them as exact in the loss of
  *                         lib/QuadAlgorithm.py:616-673; the derivative of that loss in the times, and their ordered update (ABI 17)
+ *   lfsd_time_normal_blocks / lfsd_lm_step_times   no counterpart: the Gauss-Newton matrix of the loss of lib/QuadAlgorithm.py:616-639
+ *                         in parameters AND waypoint times is an arrow (a time enters one waypoint's residuals only); its border and
+ *                         diagonal, and the Levenberg-Marquardt step with the times eliminated per waypoint (ABI 18)
  */
 #ifndef LFSD_CPDP_H
 #define LFSD_CPDP_H
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define LFSD_ABI_VERSION 17
+#define LFSD_ABI_VERSION 18
 #define LFSD_F32 0
 #define LFSD_F64 1
 #define LFSD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unknown enum) */
@@ -467,6 +470,62 @@ int lfsd_waypoint_time_grad(int dtype, int batch, int n_grid, int n_waypoints, i
 int lfsd_tau_project(int dtype, int batch, int n_waypoints, const void* tau_ref, void* tau_io, const void* horizon,
                      const void* wp_weight, const void* tau_lo, const void* tau_hi, double max_shift,
                      const int* row_active, void* stream);
+
+/* ABI 18 -- Levenberg-Marquardt over parameters and waypoint times jointly.  With the times tau_k free, the residual block of waypoint k
+ * of a row, r_k = y(tau_k) - wp_k, has the Jacobian J_k [n_iface x p] in theta (lfsd_normal_matrix) and the column t_k [n_iface] -- the
+ * interface rows of the slope xdot(tau_k) of lfsd_waypoint_time_grad -- in tau_k, and depends on no other time.  The Gauss-Newton matrix
+ * in (theta, tau) is an arrow: H = sum_k w_k J_k^T J_k in the corner, and per waypoint
+ *   C[b][k][q] = w_k sum_c t_c X(tau_k)[q][idx_c]      (the coupling c_k = w_k J_k^T t_k;  C [B][n_waypoints][n_param])
+ *   d[b][k]    = w_k sum_c t_c t_c                     (the time block, diagonal;          d [B][n_waypoints])
+ * ("no factor 2" throughout, as H and the gradients).  lfsd_time_normal_blocks forms both: X the LINEAR interpolant of auxX_grid
+ * [B][n_grid+1][n_param][n_state] with the expressions of lfsd_normal_matrix; t from state_grid [B][n_grid+1][n_state] and, with
+ * curv = lfsd_grid_curvature of it (n_grid >= 3), along the cubic interpolant, with the expressions of lfsd_waypoint_time_grad's index
+ * path; iface_idx [n_iface] int32 (the interface compiled into a library is not served); horizon [B]; taus, wp_weight [B][n_waypoints].
+ * One thread per (row, waypoint, parameter) sums the interface components in ascending order; the weight is applied once, as (w t_c):
+ * all-ones weights give the bits of wp_weight == NULL.  A waypoint of weight exactly 0 gets +0.0 and its tau is never read (NaN padding
+ * is legal).  No atomics: a row's outputs are the same bits in any batch; a NaN row poisons only itself.  An entry of iface_idx outside
+ * [0, n_state) is found ON THE DEVICE, as lfsd_normal_matrix finds it: the call returns 0 and writes nothing.
+ * LFSD_EINVAL, before any launch: a NULL required pointer, a non-positive size, n_grid < 1 (< 3 with curv), C or d overlapping an input
+ * or each other, an unknown dtype, more than 2^31-1 workgroups. */
+int lfsd_time_normal_blocks(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                            const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
+                            const void* state_grid, const void* curv, const void* auxX_grid, void* C, void* d, void* stream);
+
+/* lfsd_lm_step with the times as unknowns: the accept / reject state machine over the point (theta, tau) and the damped solve of the
+ * arrow system, one GROUP per lane.  A group is one parameter vector and the group_size consecutive rows that learn it (B = n_groups *
+ * group_size; group_size = 1: every row its own theta); a row owns n_waypoints times.
+ * Per group (in/out), as in lfsd_lm_step: theta, grad_acc, theta_trial [G][p], loss_acc, lambda [G], H_acc [G][p][p].
+ * Per row (in/out): tau [B][K] the accepted times; tau_trial [B][K] on input the times just evaluated, on output the next (NOT yet
+ * projected) times; gtau_acc [B][K], C_acc [B][K][p], d_acc [B][K] the time gradient (lfsd_waypoint_time_grad with tau_prior = 0) and
+ * the blocks above at the accepted point; ok_acc [B] int32 the rows that counted there.
+ * Inputs: loss_t [G], grad_t [G][p], H_t [G][p][p] the evaluation at (theta_trial, tau_trial) per group -- lfsd_group_reduce's outputs,
+ * or the rows' own arrays when group_size = 1; gtau_t, C_t, d_t per row; row_ok [B] int32 or NULL (rows with 0 did not count: their
+ * values are never read); wp_weight [B][K] or NULL (weight 0: the waypoint does not exist); proj_lo [p] or NULL; group_active [G] int32
+ * or NULL (a group with 0 keeps every word of its state and of its rows'); accepted [G] int32 or NULL.  For every active group:
+ *   1. accept iff loss_t < loss_acc and loss_t, grad_t, H_t and gtau_t, C_t, d_t of the counted rows' existing waypoints are finite:
+ *      the copies of lfsd_lm_step, tau <- tau_trial for every row of the group, (gtau, C, d)_acc <- (gtau, C, d)_t for the counted rows,
+ *      ok_acc <- row_ok; lambda moves as in lfsd_lm_step;
+ *   2. under lfsd_lm_step's conditions the group cannot move: theta_trial <- theta, tau_trial <- tau;
+ *   3. with floor = 1e-8 max_j H_acc[j][j] and ftau = 1e-8 max d_acc (over the waypoints that enter): D_k = d_k + lambda (d_k + ftau),
+ *        S = H_acc + lambda (diag H_acc + floor I) - sum_k c_k c_k^T / D_k,      b = -grad_acc + sum_k c_k gtau_k / D_k,
+ *      summed rows ascending, then waypoints ascending, over the rows with ok_acc != 0 and their existing waypoints; a waypoint whose
+ *      D_k is not > 0 does not move and contributes nothing;
+ *   4. Cholesky of S without pivoting with lfsd_lm_step's retry rule (S and b are formed again for each raised lambda); solved:
+ *      theta_trial <- max(theta + dtheta, proj_lo); not solved: theta_trial <- theta, tau_trial <- tau;
+ *   5. dtau_k = -(gtau_k + c_k . dtheta) / D_k, tau_trial_k <- tau_k + dtau_k; rows that are not counted, absent and skipped waypoints
+ *      get tau_trial_k <- tau_k.
+ * With every c_k and d_k zero no correction is executed: theta, theta_trial, lambda and accepted are the bits of lfsd_lm_step.  Fixed
+ * operation order, no atomics: a group's outputs are the same bits in any batch.  Order and bounds of the proposed times are not this
+ * call's business: lfsd_tau_project(tau_ref = tau, tau_io = tau_trial, ...) follows.  The arrays must not overlap (not checked).
+ * LFSD_EINVAL: lfsd_lm_step's cases (n_groups for batch), group_size <= 0, n_waypoints <= 0, a NULL per-row array. */
+int lfsd_lm_step_times(int dtype, int n_groups, int group_size, int n_param, int n_waypoints,
+                       double lambda_down, double lambda_up, double lambda_min, double lambda_max,
+                       void* theta, void* loss_acc, void* grad_acc, void* H_acc, void* lambda, void* theta_trial,
+                       void* tau, void* tau_trial, void* gtau_acc, void* C_acc, void* d_acc, int* ok_acc,
+                       const void* loss_t, const void* grad_t, const void* H_t,
+                       const void* gtau_t, const void* C_t, const void* d_t,
+                       const int* row_ok, const void* wp_weight, const void* proj_lo,
+                       const int* group_active, int* accepted, void* stream);
 
 /* ABI 10 -- the per-seed stop rule of the learning loop.  The reference learns every seed on its own and leaves its loop when
  * `loss > 0.9 and norm(diff_loss) > 0.05` fails (lib/QuadAlgorithm.py:239-257; Examples/robotarm_random.py:60-73 solve the seeds

@@ -825,9 +825,24 @@ class SparseDemoLearner:
     rules and per-row rule lists, ``interplation_level=2``, ``waypoint_weights`` / ``n_waypoints`` / ``pad_demonstrations`` (an absent
     waypoint has gradient +0 and is never read or moved), ``warm_start``, ``skip_unconverged``, ``trace`` and
     ``true_loss_print_flag`` (the second evaluation runs at ``taus``).  Refused with ``LfsdError``: ``loss_fn``, ``method="LM"`` (the
-    joint Gauss-Newton step needs the tau columns eliminated per waypoint), ``stop_rule`` (its gather of ``taus`` runs only when the
+    first-order update of the times does not run beside the LM step: ``lm_taus`` below takes the joint step), ``stop_rule`` (its gather of ``taus`` runs only when the
     set shrinks), initial times that are not strictly increasing inside [0, horizon] among the existing waypoints, and
     ``tau_learning_rate=None``.
+
+    ``lm_taus`` (default ``False`` = every learner makes the launches it made; ``method="LM"`` only): the waypoint times become unknowns of
+    the Levenberg-Marquardt step.  A time enters the residuals of its own waypoint only, so the Gauss-Newton matrix in (theta, tau) is an
+    arrow: H, a border ``c_k = w_k J_k^T t_k`` and a diagonal ``d_k = w_k t_k^T t_k`` with t_k the interface rows of the slope xdot(tau_k).
+    One step: the evaluation at (``theta_trial``, ``tau_trial``) with the sensitivity grids; ``lfsd_normal_matrix``;
+    ``lfsd_waypoint_time_grad`` without a prior; ``lfsd_time_normal_blocks`` (C, d); in grouped mode ``lfsd_group_reduce``;
+    ``lfsd_lm_step_times`` -- accept / reject over the whole point, the times eliminated per waypoint, the p x p solve, the times by
+    back-substitution (``group_size = demos_per_seed``, ``row_ok`` from ``skip_unconverged``); ``lfsd_tau_project`` of ``tau_trial``
+    against the accepted times (``tau_max_shift``, ``tau_bounds``).  ``taus`` are the ACCEPTED times, ``tau_trial`` the next ones,
+    ``tau_grad`` the last time gradient, ``tau0`` the demonstrated times, ``time_blocks`` the pair (C [B, K, p], d [B, K]) at the accepted
+    point; ``step()`` returns loss and gradient at the trial point as LM does.  It combines with independent and grouped mode,
+    ``waypoint_weights`` / ``n_waypoints``, ``interplation_level=2``, ``warm_start``, ``skip_unconverged`` and ``trace``.  Refused with
+    ``LfsdError``: without ``method="LM"``; with ``learn_taus``; ``tau_learning_rate`` / ``tau_method`` / ``tau_prior`` (a prior term is not
+    part of this step's objective); what ``method="LM"`` refuses; ``stop_rule``; initial times that are not strictly increasing.  A row
+    needs more residuals than unknowns (K n_iface > p + K) for its times to be identified.
     """
 
     def __init__(self, oc, ini_state, horizon, taus, waypoints, interface_idx, theta0, method="Vanilla",
@@ -836,17 +851,35 @@ class SparseDemoLearner:
                  skip_unconverged=None, stop_rule=None, interplation_level=1, loss_fn=None, grad_scale=1.0, trace=None,
                  lm_lambda0=1e-2, lm_down=1.0 / 3.0, lm_up=2.0, lm_min=1e-8, lm_max=1e8, demos_per_seed=None,
                  waypoint_weights=None, n_waypoints=None, learn_taus=False, tau_learning_rate=None, tau_method=None,
-                 tau_max_shift=0.25, tau_bounds=None, tau_prior=0.0):
+                 tau_max_shift=0.25, tau_bounds=None, tau_prior=0.0, lm_taus=False):
         self.oc, self.method, self.lr, self.mu = oc, method, learning_rate, mu
         self._tau = None              # state of the learnable waypoint times (learn_taus), None: the times are data
         self._tau_pt = None           # the times the next evaluation runs at when they differ from `taus` (the look-ahead point)
+        self._lmt = None              # state of the times inside the Levenberg-Marquardt step (lm_taus)
         self.tau_grad = None
+        if lm_taus:
+            if learn_taus:
+                raise LfsdError("learn_taus and lm_taus are two ways of learning the times (a first-order rule beside theta's update, or "
+                                "inside the joint step of method='LM'): give one")
+            if method != "LM":
+                raise LfsdError("lm_taus puts the waypoint times into the Levenberg-Marquardt step: method='LM' only (got %r; "
+                                "learn_taus=True learns them under the first-order rules)" % (method,))
+            given = [nm for nm, v in (("tau_learning_rate", tau_learning_rate), ("tau_method", tau_method)) if v is not None]
+            if not (isinstance(tau_prior, (int, float)) and float(tau_prior) == 0.0):
+                given.append("tau_prior")
+            if given:
+                raise LfsdError("%s with lm_taus: the joint step has no learning rate or rule of its own for the times, and a prior "
+                                "term is not part of this step's objective (the sum of squares of the waypoint residuals)" % ", ".join(given))
+            if stop_rule is not None:
+                raise LfsdError("lm_taus does not combine with stop_rule yet: the dense batch gathers taus only when the set of "
+                                "seeds shrinks, moving times would need it every step")
         if learn_taus:
             if loss_fn is not None:
                 raise LfsdError("learn_taus differentiates the fused waypoint loss in its times: a loss_fn samples taus on its own")
             if method == "LM":
-                raise LfsdError("learn_taus with method='LM': the joint Gauss-Newton step needs the tau columns eliminated per "
-                                "waypoint (a follow-up, DESIGN.md section 17); use one of the five first-order rules")
+                raise LfsdError("learn_taus with method='LM': the first-order update of the times does not run beside the LM step; "
+                                "lm_taus=True takes the joint Gauss-Newton step over theta and the times (DESIGN.md section 18), or use "
+                                "one of the five first-order rules")
             if stop_rule is not None:
                 raise LfsdError("learn_taus does not combine with stop_rule yet: the dense batch gathers taus only when the set of "
                                 "seeds shrinks, moving times would need it every step")
@@ -973,6 +1006,8 @@ class SparseDemoLearner:
         self.tau0 = self.taus
         if learn_taus:
             self._init_taus(tau_learning_rate, tau_method, tau_max_shift, tau_bounds, tau_prior)
+        if lm_taus:
+            self._init_lm_taus(tau_max_shift, tau_bounds)
         # warm_start: start every OC solve from the previous iteration's controls (theta moves little per step).
         # The reference cold-starts IPOPT every time; the converged KKT point is the same, only the path to it is shorter.
         self.warm_start = warm_start
@@ -1050,21 +1085,17 @@ class SparseDemoLearner:
         return {} if wts is None else dict(waypoint_weights=wts)
 
     # ---- learnable waypoint times (ABI 17) ---------------------------------------------------------------------------------
-    def _init_taus(self, lr, method, max_shift, bounds, prior):
-        """State of ``learn_taus``: the times become a [B, K] array of their own with optimizer moments, checked once, here."""
+    def _check_tau_args(self, who, max_shift, bounds, prior=None):
+        """What learn_taus and lm_taus share, checked once: ``tau_max_shift`` in (0, 0.5), the initial times strictly increasing among
+        the existing waypoints, ``tau_bounds``; ``tau_prior`` of learn_taus in the place it always had among them.  Returns (c, lo [B, K]
+        or None, hi [B, K] or None)."""
         B, K = self.taus.shape
         dt, dev = self.taus.dtype, self.taus.device
-        if method is None:
-            method = self.method if isinstance(self.method, str) else "Vanilla"
-        if not isinstance(method, str) or method not in runtime.OPT_METHODS or method == "LM":
-            raise LfsdError("tau_method is one of the five first-order rules (got %r)" % (method,))
-        lr, c, prior = float(lr), float(max_shift), float(prior)
-        if not (np.isfinite(lr) and lr >= 0):
-            raise LfsdError("tau_learning_rate must be finite and non-negative (got %r)" % (lr,))
+        c = float(max_shift)
         if not 0 < c < 0.5:
             raise LfsdError("tau_max_shift must lie in (0, 0.5): a time moves by at most that fraction of the gap to its neighbour "
                             "per step, so the order cannot invert (got %r)" % (c,))
-        if not (np.isfinite(prior) and prior >= 0):
+        if prior is not None and not (np.isfinite(prior) and prior >= 0):
             raise LfsdError("tau_prior must be finite and non-negative (got %r)" % (prior,))
         # the initial times: strictly increasing inside [0, horizon] among the waypoints that exist (one host read, at set-up)
         t = self.taus.detach().double().cpu().numpy()
@@ -1073,8 +1104,8 @@ class SparseDemoLearner:
         for b in range(B):
             tb = t[b] if w is None else t[b][w[b] != 0]
             if tb.size and not (np.all(np.isfinite(tb)) and tb[0] >= 0 and tb[-1] <= hz[b] and np.all(np.diff(tb) > 0)):
-                raise LfsdError("learn_taus needs initial taus strictly increasing inside [0, horizon] among the existing waypoints "
-                                "(row %d: %s, horizon %g)" % (b, tb.tolist(), hz[b]))
+                raise LfsdError("%s needs initial taus strictly increasing inside [0, horizon] among the existing waypoints "
+                                "(row %d: %s, horizon %g)" % (who, b, tb.tolist(), hz[b]))
         lo = hi = None
         if bounds is not None:
             if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
@@ -1090,6 +1121,20 @@ class SparseDemoLearner:
                     raise LfsdError("tau_bounds %s holds a NaN" % nm)
                 both.append(x.to(device=dev, dtype=dt).contiguous())
             lo, hi = both
+        return c, lo, hi
+
+    def _init_taus(self, lr, method, max_shift, bounds, prior):
+        """State of ``learn_taus``: the times become a [B, K] array of their own with optimizer moments, checked once, here."""
+        B, K = self.taus.shape
+        dt, dev = self.taus.dtype, self.taus.device
+        if method is None:
+            method = self.method if isinstance(self.method, str) else "Vanilla"
+        if not isinstance(method, str) or method not in runtime.OPT_METHODS or method == "LM":
+            raise LfsdError("tau_method is one of the five first-order rules (got %r)" % (method,))
+        lr, prior = float(lr), float(prior)
+        if not (np.isfinite(lr) and lr >= 0):
+            raise LfsdError("tau_learning_rate must be finite and non-negative (got %r)" % (lr,))
+        c, lo, hi = self._check_tau_args("learn_taus", max_shift, bounds, prior)
         self.tau0 = self.taus.clone()         # the demonstrated times: tau_ref of the prior
         self.taus = self.taus.clone()         # (the learner's own array: the caller's tensor is never written)
         z = lambda: torch.zeros((B, K), dtype=dt, device=dev)
@@ -1141,6 +1186,45 @@ class SparseDemoLearner:
                                 m=s["m"], v=s["v"], vhat=s["vhat"], proj_lo=None, row_active=row_active)
         self.lib.tau_project(s["start"], self.taus, self.hz, s["c"], wp_weight=self.wts, tau_lo=s["lo"], tau_hi=s["hi"],
                              row_active=row_active)
+
+    # ---- the times inside the Levenberg-Marquardt step (lm_taus, ABI 18) -------------------------------------------------------
+    def _init_lm_taus(self, max_shift, bounds):
+        """State of ``lm_taus``: ``taus`` becomes the learner's own array of ACCEPTED times beside ``tau_trial``, with the time
+        gradient and the border / diagonal of the arrow matrix at the accepted point, per row."""
+        c, lo, hi = self._check_tau_args("lm_taus", max_shift, bounds)
+        B, K = self.taus.shape
+        p = self.theta.shape[1]
+        dt, dev = self.theta.dtype, self.taus.device
+        z = lambda *s: torch.zeros(s, dtype=dt, device=dev)
+        self.tau0 = self.taus.clone()
+        self.taus = self.taus.clone()         # (the learner's own array: the caller's tensor is never written)
+        self._lmt = dict(c=c, lo=lo, hi=hi, trial=self.taus.clone(), gtau=z(B, K), C=z(B, K, p), d=z(B, K),
+                         ok=torch.zeros(B, dtype=torch.int32, device=dev), gtau_t=None, C_t=None, d_t=None)
+        self.tau_grad = z(B, K)
+
+    tau_trial = property(lambda self: None if self._lmt is None else self._lmt["trial"],
+                         doc="[B, K] the times step() evaluates next (lm_taus; taus: the accepted times)")
+    time_blocks = property(lambda self: None if self._lmt is None else (self._lmt["C"], self._lmt["d"]),
+                           doc="(C [B, K, p], d [B, K]): coupling and time block of the Gauss-Newton matrix at the accepted point (lm_taus)")
+
+    def _lm_time_terms(self, taus):
+        """Of the evaluation just made at the times `taus` (in step(): tau_trial): dLoss/dtau without a prior (lfsd_waypoint_time_grad) and the
+        coupling / time blocks (lfsd_time_normal_blocks), in the sweeps' dtype, cast to theta's.  Two launches."""
+        s, sol, aux = self._lmt, self._sol, self._aux
+        hook = self.event_hook
+        ad = aux["loss"].dtype
+        cv = lambda t: None if t is None else t.to(ad).contiguous()
+        curv = aux["curvature"][0] if aux.get("curvature") is not None else None
+        X, hz, taus, wts = cv(sol["state_grid"]), cv(self.hz), cv(taus), cv(self.wts)
+        if hook is not None:
+            hook("tau_grad")
+        g = self.lib.waypoint_time_grad(X, hz, taus, cv(self.wps), self.iface, curv=curv, wp_weight=wts)
+        if hook is not None:
+            hook("time_blocks")
+        C, d = self.lib.time_normal_blocks(X, hz, taus, aux["auxX_grid"], self.iface, curv=curv, wp_weight=wts)
+        dt = self.theta.dtype
+        s["gtau_t"], s["C_t"], s["d_t"] = g.to(dt), C.to(dt), d.to(dt)
+        self.tau_grad = s["gtau_t"]
 
     # ---- per-row update rules (hyper-parameter sweeps in one batch) and device traces -------------------------------------
     @staticmethod
@@ -1212,7 +1296,18 @@ class SparseDemoLearner:
         return self.lib.lookahead_rows(self._method_rows, self._hyper, self.theta, self.m)
 
     def _update(self, grad, row_active, loss=None):
-        if self._lm is not None:      # accept / reject the point just evaluated and solve for the next one (lfsd_lm_step)
+        if self._lmt is not None:     # the same over (theta, tau): lfsd_lm_step_times, then the proposed times are put in order
+            s, t = self._lm, self._lmt
+            D = self.demos_per_seed or 1
+            row_ok = None if self._ok is None else self._ok.to(torch.int32)
+            self.lib.lm_step_times(self.theta, s["loss"], s["grad"], s["H"], s["lam"], self.theta_trial, self.taus, t["trial"], t["gtau"],
+                                   t["C"], t["d"], t["ok"], loss.contiguous(), grad.contiguous(), self._H_t, t["gtau_t"].contiguous(),
+                                   t["C_t"].contiguous(), t["d_t"].contiguous(), group_size=D, lambda_down=s["down"], lambda_up=s["up"],
+                                   lambda_min=s["lo"], lambda_max=s["hi"], row_ok=row_ok, wp_weight=self.wts, proj_lo=self.proj_lo,
+                                   group_active=row_active, accepted=s["accepted"])
+            rows = row_active if row_active is None or D == 1 else row_active.repeat_interleave(D).contiguous()
+            self.lib.tau_project(self.taus, t["trial"], self.hz, t["c"], wp_weight=self.wts, tau_lo=t["lo"], tau_hi=t["hi"], row_active=rows)
+        elif self._lm is not None:      # accept / reject the point just evaluated and solve for the next one (lfsd_lm_step)
             s = self._lm
             self.lib.lm_step(self.theta, s["loss"], s["grad"], s["H"], s["lam"], self.theta_trial, loss.contiguous(), grad.contiguous(),
                              self._H_t, lambda_down=s["down"], lambda_up=s["up"], lambda_min=s["lo"], lambda_max=s["hi"],
@@ -1327,7 +1422,9 @@ class SparseDemoLearner:
         if lm:
             if hook is not None:
                 hook("normal_matrix")
-            self._H_t = self._normal_matrix(self._aux, self.hz, self.taus, self.wts)
+            self._H_t = self._normal_matrix(self._aux, self.hz, taus, self.wts)
+            if self._lmt is not None:
+                self._lm_time_terms(taus)
         loss, grad = self._aux["loss"].to(self.theta.dtype), self._aux["grad"].to(self.theta.dtype)
         if self.skip_unconverged:
             loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
@@ -1597,10 +1694,12 @@ class SparseDemoLearner:
         theta_eval = self._eval_point()
         if self._tau is not None:
             self._tau_pt = self._tau_eval_point()
+        if self._lmt is not None:      # (the evaluation point is (theta_trial, tau_trial))
+            self._tau_pt = self._lmt["trial"]
         loss, grad = self._evaluate_grouped(theta_eval)
         if self._tau is not None:
             dtau = self._tau_gradient()
-            self._tau_pt = None
+        self._tau_pt = None
         hook = self.event_hook
         if hook is not None:
             hook("update")
@@ -1639,10 +1738,12 @@ class SparseDemoLearner:
         self._ok = None
         if self._tau is not None:
             self._tau_pt = self._tau_eval_point()
+        if self._lmt is not None:      # (the evaluation point is (theta_trial, tau_trial))
+            self._tau_pt = self._lmt["trial"]
         loss, grad = self.evaluate(theta_eval)
         if self._tau is not None:
             dtau = self._tau_gradient()
-            self._tau_pt = None
+        self._tau_pt = None
         hook = self.event_hook
         if hook is not None:
             hook("update")

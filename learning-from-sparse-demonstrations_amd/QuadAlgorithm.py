@@ -126,13 +126,15 @@ class QuadAlgorithm(object):
 
     def run(self, QuadInitialCondition, QuadDesiredStates, SparseInput, ObsList=(), print_flag=False, save_flag=False,
             initial_parameters=None, save_dir=None, stop="all", sample_all=False, waypoint_weights=None, learn_taus=False,
-            tau_learning_rate=None, tau_method=None, tau_max_shift=0.25, tau_bounds=None, tau_prior=0.0):
+            tau_learning_rate=None, tau_method=None, tau_max_shift=0.25, tau_bounds=None, tau_prior=0.0, lm_taus=False):
         """``waypoint_weights`` ([K], or [S, K] with S seeds; default None): handed to ``SparseDemoLearner`` -- a confidence per
         waypoint, zero removes it (CPDP.SparseDemoLearner).
         ``learn_taus=True, tau_learning_rate=...`` (and ``tau_method``, ``tau_max_shift``, ``tau_bounds``, ``tau_prior``; read only with ``learn_taus``): the waypoint
         times are learned beside the parameters (CPDP.SparseDemoLearner; times on the normalised horizon, as ``time_grid``); the
         results then hold ``'taus'`` [S, K], the learned times, and ``'tau_trace'``, one entry per iteration plus the start.  Not
-        together with ``stop="per_seed"``."""
+        together with ``stop="per_seed"``.
+        ``lm_taus=True`` with a Levenberg-Marquardt optimisation function (and ``tau_max_shift``, ``tau_bounds``): the joint step over
+        parameters and times (CPDP.SparseDemoLearner); ``'taus'`` are then the accepted times."""
         tau_kwargs = dict(tau_learning_rate=tau_learning_rate, tau_method=tau_method, tau_max_shift=tau_max_shift,
                           tau_bounds=tau_bounds, tau_prior=tau_prior)
         if stop not in ("all", "per_seed"):
@@ -155,9 +157,10 @@ class QuadAlgorithm(object):
                                               learning_rate=self.learning_rate, **self.opt_kwargs,
                                               **({} if waypoint_weights is None else dict(waypoint_weights=waypoint_weights)),
                                               **(dict(learn_taus=True, **tau_kwargs) if learn_taus else {}),
+                                              **(dict(lm_taus=True, tau_max_shift=tau_max_shift, tau_bounds=tau_bounds) if lm_taus else {}),
                                               **(dict(stop_rule=dict(loss=0.9, grad_norm=0.05)) if stop == "per_seed" else {}))
         self.loss_trace, self.parameter_trace = [], [self.learner.theta.cpu().numpy().copy()]
-        self.tau_trace = [self.learner.taus.cpu().numpy().copy()] if learn_taus else None
+        self.tau_trace = [self.learner.taus.cpu().numpy().copy()] if learn_taus or lm_taus else None
         loss, diff_loss_norm = 100.0, 100.0
         for j in range(self.iter_num):
             if (self.learner.n_active > 0) if stop == "per_seed" else ((loss > 0.9) and (diff_loss_norm > 0.05)):   # QuadAlgorithm.py:242
@@ -166,7 +169,7 @@ class QuadAlgorithm(object):
                 diff_loss_norm = float(torch.linalg.norm(g, dim=1).max())
                 self.loss_trace.append(l.cpu().numpy().copy())
                 self.parameter_trace.append(self.learner.theta.cpu().numpy().copy())
-                if learn_taus:
+                if learn_taus or lm_taus:
                     self.tau_trace.append(self.learner.taus.cpu().numpy().copy())
                 if print_flag:
                     print('iter:', j, ', loss:', self.loss_trace[-1], ', loss gradient norm:', diff_loss_norm)
@@ -193,7 +196,7 @@ class QuadAlgorithm(object):
             results['opt_control_traj_all'] = smp["control"].double().cpu().numpy()
         if stop == "per_seed":
             results['stop_iter'] = self.learner.stop_iter.cpu().numpy().copy()
-        if learn_taus:
+        if learn_taus or lm_taus:
             results['taus'] = self.tau_trace[-1]
             results['tau_trace'] = np.array(self.tau_trace)
         if save_flag:

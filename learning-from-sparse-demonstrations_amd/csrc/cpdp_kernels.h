@@ -26,6 +26,8 @@
 //   group_reduce_kernel   no counterpart: loss, gradient and J^T J of several demonstrations summed per seed, in a fixed order
 //   waypoint_time_grad_kernel, tau_project_kernel   no counterpart: dLoss/dtau of the waypoint loss and the ordered update of the
 //                         times, which the reference invents and then treats as exact (lib/InputWaypoints.py:212-228)
+//   time_blocks_kernel, lm_step_times_kernel   no counterpart: the coupling and time blocks of the Gauss-Newton matrix in (theta, tau)
+//                         and the Levenberg-Marquardt step with the times eliminated per waypoint
 //
 // The same source builds for the GPU with hipcc and, with -DLFSD_EMU, for the CPU
 // SIMT emulator in tests/emu (test infrastructure; never used by the product path).
@@ -34,7 +36,7 @@
 // system sweeps + loss), cpdp_opt.h (update rules), cpdp_rows.h (per-seed stop rule, row compaction / gather / scatter),
 // cpdp_spline.h (curvature fit of the cubic interpolant), cpdp_sample.h (sampling the interpolants, chain rule of a user's loss),
 // cpdp_lm.h (Gauss-Newton matrix of the waypoint loss, Levenberg-Marquardt step), cpdp_groups.h (per-group sums of several
-// demonstrations per seed), cpdp_times.h (learnable waypoint times).
+// demonstrations per seed), cpdp_times.h (learnable waypoint times), cpdp_lm_times.h (Levenberg-Marquardt over parameters and times).
 #pragma once
 #include "cpdp_common.h"
 #include "cpdp_oc.h"
@@ -46,3 +48,4 @@
 #include "cpdp_lm.h"
 #include "cpdp_groups.h"
 #include "cpdp_times.h"
+#include "cpdp_lm_times.h"

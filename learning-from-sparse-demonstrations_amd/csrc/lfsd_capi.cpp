@@ -896,3 +896,79 @@ LFSD_API int lfsd_tau_project(int dtype, int batch, int n_waypoints, const void*
                                  (const double*)wp_weight, (const double*)tau_lo, (const double*)tau_hi, max_shift, row_active};
   return lfsd_detail::launch_tau_project_f64(a, stream);
 }
+
+// ---- ABI 18: Levenberg-Marquardt over parameters and waypoint times jointly (cpdp_lm_times.h; no counterpart in the reference) ----
+LFSD_API int lfsd_time_normal_blocks(int dtype, int batch, int n_grid, int n_state, int n_param, int n_waypoints, int n_iface,
+                                     const int* iface_idx, const void* horizon, const void* taus, const void* wp_weight,
+                                     const void* state_grid, const void* curv, const void* auxX_grid, void* C, void* d,
+                                     void* stream) {
+  if (batch <= 0 || n_grid < 1 || n_state <= 0 || n_param <= 0 || n_waypoints <= 0 || n_iface <= 0) return LFSD_EINVAL;
+  if (curv && n_grid < 3) return LFSD_EINVAL;
+  if (dtype != LFSD_F32 && dtype != LFSD_F64) return LFSD_EINVAL;
+  if (!iface_idx || !horizon || !taus || !state_grid || !auxX_grid || !C || !d) return LFSD_EINVAL;
+  const unsigned long long es = dtype == LFSD_F32 ? 4 : 8, B = (unsigned long long)batch, P = (unsigned long long)n_param;
+  const unsigned long long BK = B * (unsigned long long)n_waypoints;      // (below 2^62)
+  // one thread per (row, waypoint, parameter): the launcher's workgroup limit, tested without forming a product that could wrap
+  if (BK > (0x7fffffffull * 256ull) / P) return LFSD_EINVAL;
+  const unsigned long long cb = BK * P * es, db = BK * es, gb = B * (unsigned long long)(n_grid + 1) * (unsigned long long)n_state * es;
+  const void* in[7] = {iface_idx, horizon, taus, wp_weight, state_grid, curv, auxX_grid};
+  const unsigned long long in_bytes[7] = {(unsigned long long)n_iface * sizeof(int), B * es, db, db, gb, gb, gb * P};
+  for (int i = 0; i < 7; ++i)
+    if (spans_overlap(C, cb, in[i], in_bytes[i]) || spans_overlap(d, db, in[i], in_bytes[i])) return LFSD_EINVAL;
+  if (spans_overlap(C, cb, d, db)) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    lfsd::TimeBlocksArgs<float> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const float*)horizon,
+                                  (const float*)taus, (const float*)wp_weight, (const float*)state_grid, (const float*)curv,
+                                  (const float*)auxX_grid, (float*)C, (float*)d};
+    return lfsd_detail::launch_time_blocks_f32(a, stream);
+  }
+  lfsd::TimeBlocksArgs<double> a{batch, n_grid, n_state, n_param, n_waypoints, n_iface, iface_idx, (const double*)horizon,
+                                 (const double*)taus, (const double*)wp_weight, (const double*)state_grid, (const double*)curv,
+                                 (const double*)auxX_grid, (double*)C, (double*)d};
+  return lfsd_detail::launch_time_blocks_f64(a, stream);
+}
+
+template <typename T>
+static int lm_step_times_t(int n_groups, int group_size, int n_param, int n_waypoints, double lambda_down, double lambda_up,
+                           double lambda_min, double lambda_max, void* theta, void* loss_acc, void* grad_acc, void* H_acc, void* lambda,
+                           void* theta_trial, void* tau, void* tau_trial, void* gtau_acc, void* C_acc, void* d_acc, int* ok_acc,
+                           const void* loss_t, const void* grad_t, const void* H_t, const void* gtau_t, const void* C_t,
+                           const void* d_t, const int* row_ok, const void* wp_weight, const void* proj_lo, const int* group_active,
+                           int* accepted, void* stream) {
+  lfsd::LmStepTimesArgs<T> a;
+  a.n_groups = n_groups; a.group_size = group_size; a.n_param = n_param; a.n_waypoints = n_waypoints;
+  a.lambda_down = (T)lambda_down; a.lambda_up = (T)lambda_up; a.lambda_min = (T)lambda_min; a.lambda_max = (T)lambda_max;
+  a.theta = (T*)theta; a.loss_acc = (T*)loss_acc; a.grad_acc = (T*)grad_acc; a.H_acc = (T*)H_acc; a.lambda = (T*)lambda;
+  a.theta_trial = (T*)theta_trial; a.tau = (T*)tau; a.tau_trial = (T*)tau_trial; a.gtau_acc = (T*)gtau_acc; a.C_acc = (T*)C_acc;
+  a.d_acc = (T*)d_acc; a.ok_acc = ok_acc; a.loss_t = (const T*)loss_t; a.grad_t = (const T*)grad_t; a.H_t = (const T*)H_t;
+  a.gtau_t = (const T*)gtau_t; a.C_t = (const T*)C_t; a.d_t = (const T*)d_t; a.row_ok = row_ok; a.wp_weight = (const T*)wp_weight;
+  a.proj_lo = (const T*)proj_lo; a.group_active = group_active; a.accepted = accepted;
+  if constexpr (sizeof(T) == 4) return lfsd_detail::launch_lm_step_times_f32(a, stream);
+  else return lfsd_detail::launch_lm_step_times_f64(a, stream);
+}
+
+LFSD_API int lfsd_lm_step_times(int dtype, int n_groups, int group_size, int n_param, int n_waypoints, double lambda_down,
+                                double lambda_up, double lambda_min, double lambda_max, void* theta, void* loss_acc, void* grad_acc,
+                                void* H_acc, void* lambda, void* theta_trial, void* tau, void* tau_trial, void* gtau_acc, void* C_acc,
+                                void* d_acc, int* ok_acc, const void* loss_t, const void* grad_t, const void* H_t, const void* gtau_t,
+                                const void* C_t, const void* d_t, const int* row_ok, const void* wp_weight, const void* proj_lo,
+                                const int* group_active, int* accepted, void* stream) {
+  if (n_groups <= 0 || group_size <= 0 || n_waypoints <= 0 || n_param <= 0 || n_param > lfsd::LM_MAX_PARAM) return LFSD_EINVAL;
+  if (!theta || !loss_acc || !grad_acc || !H_acc || !lambda || !theta_trial || !loss_t || !grad_t || !H_t) return LFSD_EINVAL;
+  if (!tau || !tau_trial || !gtau_acc || !C_acc || !d_acc || !ok_acc || !gtau_t || !C_t || !d_t) return LFSD_EINVAL;
+  // (every comparison is false for a NaN: written so that a NaN scalar fails one of them)
+  if (!(lambda_down > 0 && lambda_down <= 1) || !(lambda_up >= 1) || !(lambda_min > 0) || !(lambda_min <= lambda_max)) return LFSD_EINVAL;
+  if (dtype == LFSD_F32) {
+    // the same conditions on the values the kernel gets, as lfsd_lm_step
+    const float dn = (float)lambda_down, up = (float)lambda_up, lo = (float)lambda_min, hi = (float)lambda_max;
+    if (!(dn > 0 && dn <= 1) || !(up >= 1) || !(lo > 0) || !(lo <= hi) || !(hi <= 3.0e38f)) return LFSD_EINVAL;
+    return lm_step_times_t<float>(n_groups, group_size, n_param, n_waypoints, lambda_down, lambda_up, lambda_min, lambda_max, theta,
+                                  loss_acc, grad_acc, H_acc, lambda, theta_trial, tau, tau_trial, gtau_acc, C_acc, d_acc, ok_acc, loss_t,
+                                  grad_t, H_t, gtau_t, C_t, d_t, row_ok, wp_weight, proj_lo, group_active, accepted, stream);
+  }
+  if (dtype == LFSD_F64)
+    return lm_step_times_t<double>(n_groups, group_size, n_param, n_waypoints, lambda_down, lambda_up, lambda_min, lambda_max, theta,
+                                   loss_acc, grad_acc, H_acc, lambda, theta_trial, tau, tau_trial, gtau_acc, C_acc, d_acc, ok_acc, loss_t,
+                                   grad_t, H_t, gtau_t, C_t, d_t, row_ok, wp_weight, proj_lo, group_active, accepted, stream);
+  return LFSD_EINVAL;
+}

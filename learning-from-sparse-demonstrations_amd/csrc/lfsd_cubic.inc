@@ -1,7 +1,7 @@
 // Launchers of interpolation level 2 (ABI 11) -- the two auxiliary sweeps along the cubic interpolant and the curvature fit -- and of
 // the sampling kernels (ABI 12: cpdp_sample.h), the per-row rules (ABI 13: cpdp_opt.h) and the Levenberg-Marquardt kernels (ABI 14:
 // cpdp_lm.h), the per-group reduction (ABI 15: cpdp_groups.h), the weighted forward sweeps (ABI 16) and the kernels of the learnable waypoint
-// times (ABI 17: cpdp_times.h).  They live
+// times (ABI 17: cpdp_times.h) and of the joint Levenberg-Marquardt step (ABI 18: cpdp_lm_times.h).  They live
 // in a translation unit of their own (lfsd_cubic.cpp): the device code of the two older units is then what it was before level 2
 // existed, kernel for kernel (DESIGN.md section 11).  Single-unit builds include this file from lfsd_capi.cpp.
 namespace lfsd_detail {
@@ -170,4 +170,23 @@ template <typename T> static int launch_tau_project(const lfsd::TauProjectArgs<T
 }
 int launch_tau_project_f32(const lfsd::TauProjectArgs<float>& a, void* stream) { return launch_tau_project<float>(a, stream); }
 int launch_tau_project_f64(const lfsd::TauProjectArgs<double>& a, void* stream) { return launch_tau_project<double>(a, stream); }
+// ---- ABI 18: Levenberg-Marquardt over parameters and waypoint times jointly (cpdp_lm_times.h) ----
+// one thread per (trajectory, waypoint, parameter); the entry point has bounded the product (it stays below 2^39)
+template <typename T> static int launch_time_blocks(const lfsd::TimeBlocksArgs<T>& a, void* stream) {
+  const long long threads = (long long)a.batch * a.n_waypoints * a.n_param;
+  const long long blocks = (threads + kSplineBlock - 1) / kSplineBlock;
+  if (blocks > 0x7fffffffLL) return LFSD_EINVAL;
+  LFSD_LAUNCH((lfsd::time_blocks_kernel<T>), (unsigned)blocks, kSplineBlock, stream, a);
+  return launch_status();
+}
+int launch_time_blocks_f32(const lfsd::TimeBlocksArgs<float>& a, void* stream) { return launch_time_blocks<float>(a, stream); }
+int launch_time_blocks_f64(const lfsd::TimeBlocksArgs<double>& a, void* stream) { return launch_time_blocks<double>(a, stream); }
+// one group per lane, one wavefront per workgroup (n_groups is a positive int: at most 2^25 workgroups)
+template <typename T> static int launch_lm_step_times(const lfsd::LmStepTimesArgs<T>& a, void* stream) {
+  const unsigned grid = (unsigned)(((long long)a.n_groups + lfsd::LM_BLOCK - 1) / lfsd::LM_BLOCK);
+  LFSD_LAUNCH((lfsd::lm_step_times_kernel<T>), grid, lfsd::LM_BLOCK, stream, a);
+  return launch_status();
+}
+int launch_lm_step_times_f32(const lfsd::LmStepTimesArgs<float>& a, void* stream) { return launch_lm_step_times<float>(a, stream); }
+int launch_lm_step_times_f64(const lfsd::LmStepTimesArgs<double>& a, void* stream) { return launch_lm_step_times<double>(a, stream); }
 }

@@ -99,4 +99,9 @@ int launch_waypoint_time_grad_f32(const lfsd::TimeGradArgs<float>& a, void* stre
 int launch_waypoint_time_grad_f64(const lfsd::TimeGradArgs<double>& a, void* stream);
 int launch_tau_project_f32(const lfsd::TauProjectArgs<float>& a, void* stream);
 int launch_tau_project_f64(const lfsd::TauProjectArgs<double>& a, void* stream);
+// Levenberg-Marquardt over parameters and waypoint times jointly (ABI 18, cpdp_lm_times.h; the same third unit)
+int launch_time_blocks_f32(const lfsd::TimeBlocksArgs<float>& a, void* stream);
+int launch_time_blocks_f64(const lfsd::TimeBlocksArgs<double>& a, void* stream);
+int launch_lm_step_times_f32(const lfsd::LmStepTimesArgs<float>& a, void* stream);
+int launch_lm_step_times_f64(const lfsd::LmStepTimesArgs<double>& a, void* stream);
 }

@@ -106,7 +106,7 @@ def hipcc_commands(spec, out, extra=(), extra_capi=TUNED_CAPI, extra_riccati=TUN
 
 
 # every hand-written file a model library is compiled from (rebuild when any of them is newer than the .so)
-KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_groups.h", "cpdp_times.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
+KERNEL_SOURCES = ("cpdp_kernels.h", "cpdp_common.h", "cpdp_oc.h", "cpdp_aux.h", "cpdp_opt.h", "cpdp_rows.h", "cpdp_spline.h", "cpdp_sample.h", "cpdp_lm.h", "cpdp_groups.h", "cpdp_times.h", "cpdp_lm_times.h", "cpdp_aux_sweeps.inc", "lfsd_capi.cpp",
                   "lfsd_internal.h", "lfsd_riccati.inc", "lfsd_riccati.cpp", "lfsd_cubic.inc", "lfsd_cubic.cpp")
 
 
@@ -284,7 +284,7 @@ class ModelLibrary:
                "lfsd_aux_riccati_cubic", "lfsd_aux_forward_cubic", "lfsd_sample_grid", "lfsd_waypoint_vjp",
                "lfsd_optimizer_step_rows", "lfsd_lookahead_rows", "lfsd_trace_append", "lfsd_normal_matrix", "lfsd_lm_step",
                "lfsd_group_reduce", "lfsd_aux_forward_weighted", "lfsd_aux_forward_cubic_weighted", "lfsd_normal_matrix_weighted",
-               "lfsd_waypoint_time_grad", "lfsd_tau_project")
+               "lfsd_waypoint_time_grad", "lfsd_tau_project", "lfsd_time_normal_blocks", "lfsd_lm_step_times")
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -334,12 +334,16 @@ class ModelLibrary:
         # (ABI 17: learnable waypoint times)
         L.lfsd_waypoint_time_grad.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, cd, vp, vp]
         L.lfsd_tau_project.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, cd, vp, vp]
+        # (ABI 18: Levenberg-Marquardt over parameters and waypoint times jointly)
+        L.lfsd_time_normal_blocks.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.lfsd_lm_step_times.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lfsd_stop_compact.argtypes = [ci, ci, ci, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp, vp]
         L.lfsd_gather_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         L.lfsd_scatter_rows.argtypes = [ci, ctypes.c_longlong, vp, vp, vp, vp]
         info = _ModelInfo()
         rc = L.lfsd_get_model_info(ctypes.byref(info))
-        if rc != 0 or info.abi_version != 17:
+        if rc != 0 or info.abi_version != 18:
             raise LfsdError("ABI mismatch in %s" % path)
         self.n_state, self.n_control, self.n_auxvar, self.n_const = (info.n_state, info.n_control, info.n_auxvar,
                                                                       info.n_const)
@@ -939,6 +943,90 @@ class ModelLibrary:
                                            self._stream(tau_io))
         self._rc(rc, "lfsd_tau_project")
         return tau_io
+
+    # ---- ABI 18: Levenberg-Marquardt over parameters and waypoint times jointly ------------------------------------------------------
+    def time_normal_blocks(self, state_grid, horizon, taus, auxX_grid, iface_idx, curv=None, wp_weight=None, out=None):
+        """(C [B, K, p], d [B, K]): the coupling c_k = w_k J_k^T t_k and the time block d_k = w_k t_k^T t_k of the Gauss-Newton matrix
+        in (theta, tau) (include/lfsd_cpdp.h, ABI 18).  J_k is the linear interpolant of ``auxX_grid`` [B, n_grid+1, p, n] at ``taus``
+        [B, K] on ``iface_idx`` [n_iface] int32, t_k the interface rows of the slope of ``state_grid`` [B, n_grid+1, n] there (with
+        ``curv`` = ``grid_curvature(state_grid)`` along the cubic interpolant).  ``wp_weight`` [B, K] or None; a waypoint of weight 0
+        gets +0 and is never read.  ``out``: such a pair to write into.  Nothing is read back."""
+        if not isinstance(auxX_grid, torch.Tensor) or auxX_grid.dim() != 4 or auxX_grid.dtype not in _DT:
+            raise LfsdError("auxX_grid must be a [B, n_grid+1, n_param, n_state] float32 / float64 tensor")
+        dt = auxX_grid.dtype
+        B, N1, p, n = auxX_grid.shape
+        if not isinstance(taus, torch.Tensor) or taus.dim() != 2 or taus.shape[1] < 1:
+            raise LfsdError("taus must be a [B, K] tensor with K >= 1")
+        if not isinstance(iface_idx, torch.Tensor) or iface_idx.dim() != 1 or iface_idx.shape[0] < 1:
+            raise LfsdError("iface_idx must be an int32 tensor of at least one state component")
+        K, ni = taus.shape[1], iface_idx.shape[0]
+        if N1 < 2 or (curv is not None and N1 < 4):
+            raise LfsdError("n_grid = %d: the linear interpolant needs two nodes, the cubic one four" % (N1 - 1))
+        self._check(auxX_grid, (B, N1, p, n), dt, "auxX_grid")
+        self._check(state_grid, (B, N1, n), dt, "state_grid")
+        self._check(curv, (B, N1, n), dt, "curv", optional=True)
+        self._check(horizon, (B,), dt, "horizon")
+        self._check(taus, (B, K), dt, "taus")
+        self._check(wp_weight, (B, K), dt, "wp_weight", optional=True)
+        self._check(iface_idx, (ni,), torch.int32, "iface_idx")
+        if out is None:
+            out = (torch.empty((B, K, p), dtype=dt, device=auxX_grid.device), torch.empty((B, K), dtype=dt, device=auxX_grid.device))
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise LfsdError("out is a pair (C [B, K, p], d [B, K])")
+        C, d = out
+        self._check(C, (B, K, p), dt, "C")
+        self._check(d, (B, K), dt, "d")
+        with self._on(auxX_grid):
+            rc = self.lib.lfsd_time_normal_blocks(_DT[dt], B, N1 - 1, n, p, K, ni, self._p(iface_idx), self._p(horizon), self._p(taus),
+                                                  self._p(wp_weight), self._p(state_grid), self._p(curv), self._p(auxX_grid),
+                                                  self._p(C), self._p(d), self._stream(auxX_grid))
+        self._rc(rc, "lfsd_time_normal_blocks")
+        return C, d
+
+    def lm_step_times(self, theta, loss_acc, grad_acc, H_acc, lam, theta_trial, tau, tau_trial, gtau_acc, C_acc, d_acc, ok_acc,
+                      loss_t, grad_t, H_t, gtau_t, C_t, d_t, group_size=1, lambda_down=1.0 / 3.0, lambda_up=2.0, lambda_min=1e-8,
+                      lambda_max=1e8, row_ok=None, wp_weight=None, proj_lo=None, group_active=None, accepted=None):
+        """One Levenberg-Marquardt update over (theta, tau) of every group, in place (include/lfsd_cpdp.h, ABI 18): ``lm_step`` with
+        the times of the group's ``group_size`` rows as unknowns, eliminated per waypoint.  Per group: theta / grad_acc / theta_trial
+        / grad_t [G, p], loss_acc / lam / loss_t [G], H_acc / H_t [G, p, p].  Per row (B = G * group_size): tau / tau_trial / gtau_acc /
+        d_acc / gtau_t / d_t [B, K], C_acc / C_t [B, K, p], ok_acc [B] int32.  ``row_ok`` [B] int32, ``wp_weight`` [B, K],
+        ``group_active`` / ``accepted`` [G] int32, or None.  ``tau_trial`` comes out unprojected: ``tau_project(tau, tau_trial, ...)``
+        follows.  Nothing is read back."""
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.dtype not in _DT:
+            raise LfsdError("theta must be a [G, n_param] float32 / float64 tensor")
+        G, p = theta.shape
+        dt = theta.dtype
+        if p > 16:
+            raise LfsdError("lm_step_times factors a p x p matrix per lane: n_param = %d > 16" % p)
+        if isinstance(group_size, bool) or int(group_size) != group_size or int(group_size) <= 0:
+            raise LfsdError("group_size must be a positive integer (got %r)" % (group_size,))
+        D = int(group_size)
+        if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != G * D or tau.shape[1] < 1:
+            raise LfsdError("tau must be a [G * group_size, K] tensor with K >= 1 (G = %d, group_size = %d)" % (G, D))
+        B, K = tau.shape
+        for nm, t in (("theta", theta), ("grad_acc", grad_acc), ("theta_trial", theta_trial), ("grad_t", grad_t)):
+            self._check(t, (G, p), dt, nm)
+        for nm, t in (("loss_acc", loss_acc), ("lambda", lam), ("loss_t", loss_t)):
+            self._check(t, (G,), dt, nm)
+        for nm, t in (("H_acc", H_acc), ("H_t", H_t)):
+            self._check(t, (G, p, p), dt, nm)
+        for nm, t in (("tau", tau), ("tau_trial", tau_trial), ("gtau_acc", gtau_acc), ("d_acc", d_acc), ("gtau_t", gtau_t), ("d_t", d_t)):
+            self._check(t, (B, K), dt, nm)
+        for nm, t in (("C_acc", C_acc), ("C_t", C_t)):
+            self._check(t, (B, K, p), dt, nm)
+        self._check(ok_acc, (B,), torch.int32, "ok_acc")
+        self._check(row_ok, (B,), torch.int32, "row_ok", optional=True)
+        self._check(wp_weight, (B, K), dt, "wp_weight", optional=True)
+        self._check(proj_lo, (p,), dt, "proj_lo", optional=True)
+        self._check(group_active, (G,), torch.int32, "group_active", optional=True)
+        self._check(accepted, (G,), torch.int32, "accepted", optional=True)
+        P = self._p
+        with self._on(theta):
+            rc = self.lib.lfsd_lm_step_times(_DT[dt], G, D, p, K, float(lambda_down), float(lambda_up), float(lambda_min), float(lambda_max),
+                                             P(theta), P(loss_acc), P(grad_acc), P(H_acc), P(lam), P(theta_trial), P(tau), P(tau_trial),
+                                             P(gtau_acc), P(C_acc), P(d_acc), P(ok_acc), P(loss_t), P(grad_t), P(H_t), P(gtau_t), P(C_t),
+                                             P(d_t), P(row_ok), P(wp_weight), P(proj_lo), P(group_active), P(accepted), self._stream(theta))
+        self._rc(rc, "lfsd_lm_step_times")
 
     def stop_compact(self, loss, grad, loss_tol, grad_tol, iter_idx, rows_out, pos_out, n_out, active, stop_iter, rows_in=None,
                      eligible=None):
