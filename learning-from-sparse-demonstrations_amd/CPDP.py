@@ -404,8 +404,9 @@ class COCSys:
 
     def auxSysSolverBatch(self, sol, taus=None, waypoints=None, interface_idx=None, auxvar=None, want_grids=False,
                           Z_grid=None, out=None, phase_hook=None, validate=True, skip_status=None, interplation_level=1,
-                          waypoint_weights=None):
+                          waypoint_weights=None, auxX_grid=None, auxU_grid=None):
         """Differentiate the PMP along ``sol`` and (optionally) evaluate the sparse-waypoint loss + gradient.
+        ``Z_grid``, ``auxX_grid``, ``auxU_grid``: the caller's buffers for [P W] and (with ``want_grids``) the sensitivity grids.
         ``waypoint_weights`` ([K] or [B, K], default None = every waypoint counts once, the launches as ever): loss =
         sum_k w_k |y(tau_k) - wp_k|^2 and its gradient from the weighted forward sweep (``lfsd_aux_forward[_cubic]_weighted``).  A
         weight of zero removes the waypoint: its tau and target are never read and may be NaN padding (``pad_demonstrations``).
@@ -454,7 +455,8 @@ class COCSys:
             skip_status = ()
         return lib.aux_solve(hz, th, cs, X, U, Lm, tt, wp, ii, substeps=self.aux_substeps, want_grids=want_grids,
                              Z_grid=Z_grid, out=out, phase_hook=phase_hook, rtol=self.aux_rtol, oc_status=status,
-                             skip_status=skip_status, interp_level=interplation_level, **({} if ww is None else dict(wp_weight=ww)))
+                             skip_status=skip_status, interp_level=interplation_level, auxX_grid=auxX_grid, auxU_grid=auxU_grid,
+                             **({} if ww is None else dict(wp_weight=ww)))
 
     def _times(self, times, dtype, batch):
         tt = times if isinstance(times, torch.Tensor) else torch.as_tensor(np.asarray(times, dtype=np.float64))

@@ -548,8 +548,10 @@ class ModelLibrary:
 
     def aux_solve(self, horizon, auxvar, consts, state_grid, control_grid, costate_grid, taus, waypoints, iface_idx,
                   substeps=0, want_grids=False, Z_grid=None, out=None, phase_hook=None, rtol=1e-3, oc_status=None,
-                  skip_status=(), interp_level=1, curvature=None, wp_weight=None):
-        """``wp_weight`` [B, K] or None (include/lfsd_cpdp.h, ABI 16): a weight per waypoint, loss = sum_k w_k |r_k|^2; a zero weight
+                  skip_status=(), interp_level=1, curvature=None, wp_weight=None, auxX_grid=None, auxU_grid=None):
+        """``auxX_grid`` [B, n_grid+1, p, n] / ``auxU_grid`` [B, n_grid+1, p, m] (with ``want_grids``): the caller's buffers for the
+        sensitivity grids, as ``Z_grid`` is for [P W]; allocated here otherwise.
+        ``wp_weight`` [B, K] or None (include/lfsd_cpdp.h, ABI 16): a weight per waypoint, loss = sum_k w_k |r_k|^2; a zero weight
         removes the waypoint (its tau and target are not read); non-negative and finite, which the caller guarantees (nothing is
         read back here).  With weights the call is ``lfsd_aux_riccati`` then ``lfsd_aux_forward_weighted`` (there is no weighted
         ``lfsd_aux_solve``); None: the launches as ever.
@@ -627,9 +629,13 @@ class ModelLibrary:
             raise LfsdError("curvature tensors belong to interp_level=2")
         sfx = "_cubic" if interp_level == 2 else ""
         auxX = auxU = None
+        if (auxX_grid is not None or auxU_grid is not None) and not want_grids:
+            raise LfsdError("auxX_grid / auxU_grid buffers belong to want_grids=True")
         if want_grids:
-            auxX = torch.empty((B, N + 1, p, n), dtype=dt, device=dev)
-            auxU = torch.empty((B, N + 1, p, m), dtype=dt, device=dev)
+            auxX = torch.empty((B, N + 1, p, n), dtype=dt, device=dev) if auxX_grid is None else auxX_grid
+            auxU = torch.empty((B, N + 1, p, m), dtype=dt, device=dev) if auxU_grid is None else auxU_grid
+            self._check(auxX, (B, N + 1, p, n), dt, "auxX_grid")
+            self._check(auxU, (B, N + 1, p, m), dt, "auxU_grid")
         common = (_DT[dt], B, N, self._p(horizon), self._p(auxvar), self._p(consts), per_traj,
                   self._p(state_grid), self._p(control_grid), self._p(costate_grid)) + curv + (self._p(Z_grid),)
         tail = (nw, ni, self._p(iface_idx), self._p(taus), self._p(waypoints), self._p(out["loss"]),
