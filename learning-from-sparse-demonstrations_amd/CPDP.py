@@ -1159,21 +1159,26 @@ class SparseDemoLearner:
         look = self.lib.lookahead(self.taus, s["m"], s["mu"])
         return self.lib.tau_project(self.taus, look, self.hz, s["c"], wp_weight=self.wts, tau_lo=s["lo"], tau_hi=s["hi"])
 
-    def _tau_gradient(self):
-        """dLoss/dtau (no factor 2) of the evaluation just made, from its solved state grid: one launch (lfsd_waypoint_time_grad)."""
-        s, sol, aux = self._tau, self._sol, self._aux
-        if self.event_hook is not None:
-            self.event_hook("tau_grad")
-        ad = aux["loss"].dtype                        # (the sweeps' arithmetic: at level 2 the curvature grid is in it)
+    def _time_inputs(self):
+        """What the kernels of the waypoint times read of the evaluation just made, in the sweeps' dtype (at level 2 the curvature grid
+        is in it): the cast, the state grid's curvature grid or None, the state grid, the horizons and the times in use."""
+        sol, aux = self._sol, self._aux
+        ad = aux["loss"].dtype
         cv = lambda t: None if t is None else t.to(ad).contiguous()
         curv = aux["curvature"][0] if aux.get("curvature") is not None else None
         taus = self.taus if self._tau_pt is None else self._tau_pt
-        consts = None
-        if self.iface is None:
-            consts = cv(sol["consts"])
-        g = self.lib.waypoint_time_grad(cv(sol["state_grid"]), cv(self.hz), cv(taus), cv(self.wps), self.iface, curv=curv,
-                                        consts=consts, wp_weight=cv(self.wts), tau_ref=cv(self.tau0) if s["prior"] > 0 else None,
-                                        tau_prior=s["prior"], out=self.tau_grad if ad == self.tau_grad.dtype else None)
+        return cv, curv, cv(sol["state_grid"]), cv(self.hz), cv(taus)
+
+    def _tau_gradient(self):
+        """dLoss/dtau (no factor 2) of the evaluation just made, from its solved state grid: one launch (lfsd_waypoint_time_grad)."""
+        s = self._tau
+        if self.event_hook is not None:
+            self.event_hook("tau_grad")
+        cv, curv, X, hz, taus = self._time_inputs()
+        consts = cv(self._sol["consts"]) if self.iface is None else None
+        g = self.lib.waypoint_time_grad(X, hz, taus, cv(self.wps), self.iface, curv=curv, consts=consts, wp_weight=cv(self.wts),
+                                        tau_ref=cv(self.tau0) if s["prior"] > 0 else None, tau_prior=s["prior"],
+                                        out=self.tau_grad if X.dtype == self.tau_grad.dtype else None)
         self.tau_grad = g.to(self.taus.dtype)
         return self.tau_grad
 
@@ -1209,21 +1214,18 @@ class SparseDemoLearner:
     time_blocks = property(lambda self: None if self._lmt is None else (self._lmt["C"], self._lmt["d"]),
                            doc="(C [B, K, p], d [B, K]): coupling and time block of the Gauss-Newton matrix at the accepted point (lm_taus)")
 
-    def _lm_time_terms(self, taus):
-        """Of the evaluation just made at the times `taus` (in step(): tau_trial): dLoss/dtau without a prior (lfsd_waypoint_time_grad) and the
+    def _lm_time_terms(self):
+        """Of the evaluation just made (in step(): at tau_trial): dLoss/dtau without a prior (lfsd_waypoint_time_grad) and the
         coupling / time blocks (lfsd_time_normal_blocks), in the sweeps' dtype, cast to theta's.  Two launches."""
-        s, sol, aux = self._lmt, self._sol, self._aux
-        hook = self.event_hook
-        ad = aux["loss"].dtype
-        cv = lambda t: None if t is None else t.to(ad).contiguous()
-        curv = aux["curvature"][0] if aux.get("curvature") is not None else None
-        X, hz, taus, wts = cv(sol["state_grid"]), cv(self.hz), cv(taus), cv(self.wts)
+        s, hook = self._lmt, self.event_hook
+        cv, curv, X, hz, taus = self._time_inputs()
+        wts = cv(self.wts)
         if hook is not None:
             hook("tau_grad")
         g = self.lib.waypoint_time_grad(X, hz, taus, cv(self.wps), self.iface, curv=curv, wp_weight=wts)
         if hook is not None:
             hook("time_blocks")
-        C, d = self.lib.time_normal_blocks(X, hz, taus, aux["auxX_grid"], self.iface, curv=curv, wp_weight=wts)
+        C, d = self.lib.time_normal_blocks(X, hz, taus, self._aux["auxX_grid"], self.iface, curv=curv, wp_weight=wts)
         dt = self.theta.dtype
         s["gtau_t"], s["C_t"], s["d_t"] = g.to(dt), C.to(dt), d.to(dt)
         self.tau_grad = s["gtau_t"]
@@ -1321,14 +1323,6 @@ class SparseDemoLearner:
             self.lib.optimizer_step_rows(self._method_rows, self._hyper, self.theta, grad, self.iter_idx, self.m, self.v, self.vhat,
                                          proj_lo=self.proj_lo, row_active=row_active)
 
-    def _start_state(self):
-        """(controls, status) the next solve of the rows now evaluated starts from (warm_start / skip_unconverged), or None."""
-        if not (self.warm_start or self.skip_unconverged):
-            return None
-        if self._stop is not None and self.n_active < self.B:
-            return self._prev
-        return None if self._sol is None else (self._sol["control_grid"], self._sol["status"])
-
     def _second_evaluation(self, evaluate, flag):
         """The evaluation at theta that flagged Nesterov rows take their loss and gradient from (QuadAlgorithm.py:487-492), run on
         the whole (active) batch.  Every OTHER row is left as its uniform learner leaves it, which has no second evaluation: the
@@ -1382,88 +1376,125 @@ class SparseDemoLearner:
             return torch.zeros(self.B, dtype=torch.int32, device=self.x0.device)
         return self._stop_iter
 
+    # ---- one evaluation: the rows being evaluated, their solve and their sweeps ------------------------------------------------
     def evaluate(self, theta):
         """(loss [B], grad [B,p]) of every trajectory at parameters theta ([B,p] or [1,p]).  mode='grouped': the group sums
         (loss [G], grad [G,p]) at theta [G,p] or [1,p]; any other shape is refused."""
         if self.mode == "grouped":
-            return self._evaluate_grouped(theta)
-        return self._evaluate_rows(theta)
+            G, p = self.theta.shape
+            if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] != p or theta.shape[0] not in (1, G) \
+                    or theta.dtype != self.theta.dtype:
+                raise LfsdError("mode='grouped' evaluates theta [%d, %d] (or [1, %d], expanded to the groups) of dtype %s, got %s"
+                                % (G, p, p, self.theta.dtype, (tuple(theta.shape), theta.dtype) if isinstance(theta, torch.Tensor) else type(theta)))
+            if theta.shape[0] != G:      # (the index row -> row // D reaches G - 1: the gather must find G rows)
+                theta = theta.expand(G, p)
+        return self._evaluate(theta, dense=False)
 
-    def _evaluate_rows(self, theta):
-        th = theta if theta.shape[0] == self.B else theta.expand(self.B, -1).contiguous()
+    def _start_state(self, dense=None):
+        """(controls, status) the next solve of the rows now evaluated starts from (warm_start / skip_unconverged), or None."""
+        if not (self.warm_start or self.skip_unconverged):
+            return None
+        if self._dense_now() if dense is None else dense:
+            return self._prev
+        return None if self._sol is None else (self._sol["control_grid"], self._sol["status"])
+
+    def _dense_now(self):
+        """A stop rule has stopped seeds: the solve and the sweeps run on the dense batch of the others."""
+        return self._stop is not None and self.n_active < self.B
+
+    def _rows_view(self, dense):
+        """The rows being evaluated: their number, the per-row inputs, the (controls, status) their solve starts from and the buffers
+        the solve and the sweeps write -- reused from step to step.  Full batch: the learner's own tensors and the outputs of its last
+        evaluation.  Dense (after seeds have stopped): the leading n_active rows of the dense copies and of the full-size buffers."""
+        start = self._start_state(dense)
+        if not dense:
+            taus = self.taus if self._tau_pt is None else self._tau_pt      # (learned times: their look-ahead or trial point)
+            return dict(n=self.B, dense=False, x0=self.x0, hz=self.hz, taus=taus, wps=self.wps, wts=self.wts, consts=self.consts,
+                        start=start, sol_out=self._sol_out(), aux_out=self._aux_out(), Z=self._Z)
+        n, d, full = self.n_active, self._dense, self._full
+        lead = lambda k, absent=None: d[k][:n] if k in d else absent
+        return dict(n=n, dense=True, x0=lead("x0"), hz=lead("hz"), taus=lead("taus"), wps=lead("wps"), wts=lead("wts"),
+                    consts=lead("consts", self.consts), start=None if start is None else tuple(t[:n] for t in start),
+                    sol_out={k: t[:n] for k, t in full["sol"].items()}, aux_out={k: t[:n] for k, t in full["aux"].items()},
+                    Z=full["Z"][:n])
+
+    def _evaluate_view(self, view, theta):
+        """(loss [n], grad [n,p]) of the rows of `view` at theta [n,p]: the solve, the two sweeps (fused loss, or the sensitivity grids
+        and `loss_fn`), for method='LM' the Gauss-Newton matrix (and the time terms of lm_taus), the casts to theta's dtype, the mask
+        of skip_unconverged."""
+        oc, hook = self.oc, self.event_hook
         u_init = None
-        if self.warm_start and self._sol is not None:
-            u_init = self._sol["control_grid"][:, :-1].contiguous()
-        elif self.skip_unconverged and self._sol is not None:
-            # a solve that ran out of iterations is continued from where it stopped instead of restarted (its parameters
-            # did not move, a cold start would fail the same way); all others start from zero controls = cold start
-            cont = (self._sol["status"] == 3).reshape(-1, 1, 1)
-            prev = self._sol["control_grid"][:, :-1]
-            u_init = torch.where(cont & torch.isfinite(prev), prev, torch.zeros_like(prev)).contiguous()
-        hook = self.event_hook
+        if view["start"] is not None:
+            prev, status = view["start"][0][:, :-1], view["start"][1]
+            if self.warm_start:
+                u_init = prev.contiguous()
+            elif self.skip_unconverged:
+                # a solve that ran out of iterations is continued from where it stopped instead of restarted (its parameters
+                # did not move, a cold start would fail the same way); all others start from zero controls = cold start
+                cont = (status == 3).reshape(-1, 1, 1)
+                u_init = torch.where(cont & torch.isfinite(prev), prev, torch.zeros_like(prev)).contiguous()
         if hook is not None:
             hook("oc_solve")
-        self._sol = self.oc.cocSolverBatch(self.x0, self.hz, th, consts=self.consts, u_init=u_init,
-                                           workspace=self._ws, out=self._sol_out())
-        self._ws = self._sol["workspace"]
-        phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
-        if self.loss_fn is not None:
-            loss, grad = self._evaluate_loss_fn(phase)
-            if self.skip_unconverged:
-                loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
-            return loss, grad
+        sol = oc.cocSolverBatch(view["x0"], view["hz"], theta, consts=view["consts"], u_init=u_init, workspace=self._ws,
+                                out=view["sol_out"])
+        self._ws = sol["workspace"]
         # a learner that freezes unconverged rows anyway does not pay for differentiating them (they are masked by their
         # status below): the diverged seeds of a fixed learning rate otherwise hold the Riccati launch 20x longer
+        kw = dict(Z_grid=view["Z"], out=view["aux_out"], validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
+                  phase_hook=None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None),
+                  interplation_level=self.interplation_level)
         lm = self._lm is not None                        # (LM: the sensitivity grids are written too, J^T J is formed from them)
-        taus = self.taus if self._tau_pt is None else self._tau_pt      # (learn_taus under Nesterov: the projected look-ahead times)
-        self._aux = self.oc.auxSysSolverBatch(self._sol, taus, self.wps, self.iface, want_grids=lm, Z_grid=self._Z,
-                                              out=self._aux_out(), phase_hook=phase, validate=False,
-                                              skip_status=(3, 4) if self.skip_unconverged else None,
-                                              interplation_level=self.interplation_level, **self._wkw(self.wts))
-        self._Z = self._aux["Z_grid"]
-        if lm:
-            if hook is not None:
-                hook("normal_matrix")
-            self._H_t = self._normal_matrix(self._aux, self.hz, taus, self.wts)
-            if self._lmt is not None:
-                self._lm_time_terms(taus)
-        loss, grad = self._aux["loss"].to(self.theta.dtype), self._aux["grad"].to(self.theta.dtype)
+        if self.loss_fn is not None:
+            aux = oc.auxSysSolverBatch(sol, want_grids=True, **kw)
+        else:
+            aux = oc.auxSysSolverBatch(sol, view["taus"], view["wps"], self.iface, want_grids=lm, **kw, **self._wkw(view["wts"]))
+        if view["dense"]:
+            self._sol_active, self._aux_active = sol, aux
+            self._prev = (sol["control_grid"], sol["status"])
+        else:
+            self._sol, self._aux, self._Z = sol, aux, aux["Z_grid"]
+        if self.loss_fn is not None:
+            loss, grad = self._loss_fn_gradient(sol, aux, view)
+        else:
+            if lm:
+                if hook is not None:
+                    hook("normal_matrix")
+                self._H_t = self._normal_matrix(aux, view["hz"], view["taus"], view["wts"])
+                if self._lmt is not None:
+                    self._lm_time_terms()
+            loss, grad = aux["loss"].to(self.theta.dtype), aux["grad"].to(self.theta.dtype)
         if self.skip_unconverged:
-            loss, grad = self.mask_unconverged(self._sol["status"], loss, grad)
+            loss, grad = self.mask_unconverged(sol["status"], loss, grad, stats=aux.get("stats"))
         return loss, grad
 
-    def _evaluate_loss_fn(self, phase):
-        """(loss [B], grad [B,p]) of the user-written loss at the solution just computed (class docstring)."""
+    def _loss_fn_gradient(self, sol, aux, view):
+        """(loss [n], grad [n,p]) of the user-written loss at the solution `sol` with the sensitivity grids of `aux` (class docstring)."""
         oc, lib, hook = self.oc, self.lib, self.event_hook
-        self._aux = oc.auxSysSolverBatch(self._sol, want_grids=True, Z_grid=self._Z, out=self._aux_out(), phase_hook=phase,
-                                         validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
-                                         interplation_level=self.interplation_level)
-        self._Z = self._aux["Z_grid"]
         if hook is not None:
             hook("loss_fn")
-        sol = self._sol
-        if self._aux["curvature"] is not None:      # level 2: the curvature grids the sweeps fitted serve the sampling too
-            sol = dict(sol, curvature=self._aux["curvature"])
-        s = oc.sampleBatch(sol, self.taus, self.interplation_level, validate=False)
+        hz, taus = view["hz"], view["taus"]
+        if aux["curvature"] is not None:      # level 2: the curvature grids the sweeps fitted serve the sampling too
+            sol = dict(sol, curvature=aux["curvature"])
+        s = oc.sampleBatch(sol, taus, self.interplation_level, validate=False)
         with torch.enable_grad():
             x_tau = s["state"].detach().requires_grad_(True)
             u_tau = s["control"].detach().requires_grad_(True)
             loss = self.loss_fn(x_tau, u_tau)
-            if not isinstance(loss, torch.Tensor) or tuple(loss.shape) != (self.B,):
+            if not isinstance(loss, torch.Tensor) or tuple(loss.shape) != (view["n"],):
                 raise LfsdError("loss_fn must return one loss per trajectory, a [%d] tensor (got %s)"
-                                % (self.B, tuple(loss.shape) if isinstance(loss, torch.Tensor) else type(loss)))
+                                % (view["n"], tuple(loss.shape) if isinstance(loss, torch.Tensor) else type(loss)))
             rx, ru = torch.autograd.grad(loss.sum(), (x_tau, u_tau), allow_unused=True)
-        aX, aU = self._aux["auxX_grid"], self._aux["auxU_grid"]
+        aX, aU = aux["auxX_grid"], aux["auxU_grid"]
         ad = aX.dtype                               # (the sweeps' arithmetic: aux_dtype may differ from the solve's)
         cv = lambda t: t.to(ad).contiguous()
         rx = torch.zeros_like(x_tau) if rx is None else rx
-        grad = lib.waypoint_vjp(cv(self.hz), cv(self.taus), cv(rx), aX, ru=None if ru is None else cv(ru),
+        grad = lib.waypoint_vjp(cv(hz), cv(taus), cv(rx), aX, ru=None if ru is None else cv(ru),
                                 auxU_grid=None if ru is None else aU)
         if self.grad_scale != 1.0:
             grad = grad * self.grad_scale
         # a row the sweeps skipped has NaN sensitivity grids and so a NaN gradient; its loss is NaN too, as the fused loss's
         # (its solve may have left finite state grids behind)
-        status, loss = self._sol.get("status"), loss.detach()
+        status, loss = sol.get("status"), loss.detach()
         if status is not None:
             skipped = status == 4
             if self.skip_unconverged:
@@ -1497,52 +1528,67 @@ class SparseDemoLearner:
             return None
         return {k: self._aux[k] for k in ("loss", "grad", "stats")}
 
-    # ---- per-seed stop rule: the dense batch of the seeds still learning ------------------------------------------
-    def _evaluate_active(self, theta_eval):
-        """(loss [n], grad [n,p]) of the n_active < B seeds still learning, solved as a dense batch in the leading slices of the
-        buffers the full batch used.  theta_eval [B,p]."""
-        lib, n = self.lib, self.n_active
-        rows, d = self._rows[self._cur], self._dense
-        lib.gather_rows(rows, theta_eval, d["theta"], n)
-        if self._regather:               # x0 / horizon / waypoints / per-trajectory constants: only when the set shrank
-            for k, src in d["sources"].items():
-                lib.gather_rows(rows, src, d[k], n)
-            self._regather = False
-        consts = d["consts"][:n] if "consts" in d else self.consts
-        u_init = None
-        if self._prev is not None:
-            prev, status = self._prev[0][:n, :-1], self._prev[1][:n]
-            if self.warm_start:
-                u_init = prev.contiguous()
-            elif self.skip_unconverged:      # (as evaluate(): a solve at the iteration limit is continued, every other one cold-starts)
-                cont = (status == 3).reshape(-1, 1, 1)
-                u_init = torch.where(cont & torch.isfinite(prev), prev, torch.zeros_like(prev)).contiguous()
-        hook = self.event_hook
-        if hook is not None:
-            hook("oc_solve")
-        full = self._full
-        sol = self.oc.cocSolverBatch(d["x0"][:n], d["hz"][:n], d["theta"][:n], consts=consts, u_init=u_init, workspace=self._ws,
-                                     out={k: full["sol"][k][:n] for k in ("state_grid", "control_grid", "costate_grid", "cost",
-                                                                          "iters", "status")})
-        self._ws = sol["workspace"]
-        phase = None if hook is None else (lambda nm: hook("aux_" + nm) if nm != "end" else None)
+    def _evaluate(self, theta, dense=None):
+        """(loss, grad) at theta, one entry per row of theta that is evaluated: theta is brought to the rows of the view (expanded;
+        mode='grouped': lfsd_gather_rows over the groups' demonstrations; a stop rule's dense batch: lfsd_gather_rows of the seeds
+        still learning, with the inputs that do not change gathered again only when the set shrank), the view is evaluated, and the
+        mode reduces: mode='grouped' sums per group (lfsd_group_reduce: 0 plus the rows mask_unconverged left ok, ascending; with
+        method='LM' the group's H too) and returns the sums [G]; the dense batch returns its [n_active] rows -- what the stop test
+        reads -- after scattering them into the full-size ``_loss_full`` / ``_grad_full`` (and H).  `dense`: None = as the learner
+        stands, False = the full batch whatever has stopped (``evaluate()``)."""
+        lib, B = self.lib, self.B
+        dense = self._dense_now() if dense is None else dense
+        self._ok = None
+        if self.mode == "grouped":
+            th = lib.gather_rows(self._group_of_row, theta.contiguous(), self._theta_rows, B)
+        elif dense:
+            n, rows, d = self.n_active, self._rows[self._cur], self._dense
+            lib.gather_rows(rows, theta, d["theta"], n)
+            if self._regather:               # x0 / horizon / waypoints / per-trajectory constants: only when the set shrank
+                for k, src in d["sources"].items():
+                    lib.gather_rows(rows, src, d[k], n)
+                self._regather = False
+            th = d["theta"][:n]
+        else:
+            th = theta if theta.shape[0] == B else theta.expand(B, -1).contiguous()
+        loss, grad = self._evaluate_view(self._rows_view(dense), th)
         lm = self._lm is not None
-        aux = self.oc.auxSysSolverBatch(sol, d["taus"][:n], d["wps"][:n], self.iface, want_grids=lm, Z_grid=full["Z"][:n],
-                                        out={k: full["aux"][k][:n] for k in ("loss", "grad", "stats")}, phase_hook=phase,
-                                        validate=False, skip_status=(3, 4) if self.skip_unconverged else None,
-                                        interplation_level=self.interplation_level, **self._wkw(d["wts"][:n] if "wts" in d else None))
-        if lm:      # H of the dense rows goes to its seeds' rows of the full-size matrix, as loss and gradient do
-            if hook is not None:
-                hook("normal_matrix")
-            lib.scatter_rows(rows, self._normal_matrix(aux, d["hz"][:n], d["taus"][:n], d["wts"][:n] if "wts" in d else None).contiguous(), self._H_full, n)
-            self._H_t = self._H_full
-        self._sol_active, self._aux_active = sol, aux
-        self._prev = (sol["control_grid"], sol["status"])
-        loss, grad = aux["loss"].to(self.theta.dtype), aux["grad"].to(self.theta.dtype)
-        if self.skip_unconverged:
-            loss, grad = self.mask_unconverged(sol["status"], loss, grad, stats=aux.get("stats"))
+        if self.mode == "grouped":
+            self.row_loss, self.row_grad = loss, grad
+            if self.event_hook is not None:
+                self.event_hook("group_reduce")
+            row_ok = None if self._ok is None else self._ok.to(torch.int32)
+            H = self._H_t.contiguous() if lm else None
+            if self._grp_out is None:
+                G, p, dt, dev = self.n_groups, grad.shape[1], self.theta.dtype, self.theta.device
+                new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
+                self._grp_out = (new(G), new(G, p), None if H is None else new(G, p, p), torch.empty(G, dtype=torch.int32, device=dev))
+            loss, grad, H_g, self.n_ok = lib.group_reduce(loss.contiguous(), grad.contiguous(), self.demos_per_seed, H=H, row_ok=row_ok,
+                                                          out=self._grp_out)
+            if H_g is not None:
+                self._H_rows, self._H_t = self._H_t, H_g      # (what lfsd_lm_step reads: the group's J^T J)
+        elif dense:
+            if lm:      # H of the dense rows goes to its seeds' rows of the full-size matrix, as loss and gradient do
+                self._H_t = lib.scatter_rows(rows, self._H_t.contiguous(), self._H_full, n)
+            lib.scatter_rows(rows, loss.contiguous(), self._loss_full, n)
+            lib.scatter_rows(rows, grad.contiguous(), self._grad_full, n)
         return loss, grad
 
+    def _shared_sum(self, loss, grad, all_reduce):
+        """mode='shared': (loss [1], grad [1,p]) summed over the demonstrations; with `all_reduce` also over the ranks of the process
+        group, in one packed all-reduce with the number of demonstrations left out (``n_bad_device``)."""
+        g, l = grad.sum(dim=0, keepdim=True), loss.sum().reshape(1)
+        if not all_reduce:
+            return l, g
+        n_bad = (self.B - self._ok.sum()).to(g.dtype).reshape(1) if self._ok is not None else torch.zeros_like(l)
+        if self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
+            buf = torch.cat([g.reshape(-1), l, n_bad])
+            torch.distributed.all_reduce(buf, group=self.pg)              # RCCL over xGMI on the GPU
+            g, l, n_bad = buf[:-2].reshape(1, -1), buf[-2:-1], buf[-1:]
+        self.n_bad_device = n_bad                                         # (device tensor: read it outside timed loops)
+        return l, g.contiguous()
+
+    # ---- per-seed stop rule: the dense batch of the seeds still learning ------------------------------------------
     def _apply_stop_rule(self, loss, grad):
         """Stop test + compaction of the rows just evaluated (loss [n], grad [n,p], n = n_active), then the bookkeeping of a
         set that shrank.  The one host read of the rule is here."""
@@ -1580,60 +1626,6 @@ class SparseDemoLearner:
             self._prev = None
         self._cur, self.n_active, self._regather = 1 - self._cur, n_new, True
 
-    def _evaluate_stop_rule(self, theta_eval):
-        """(loss, grad) of the rows still learning -- [n_active] rows, what the stop test reads -- and full-size [B]."""
-        self._ok = None
-        n = self.n_active
-        if n == self.B:
-            loss, grad = self.evaluate(theta_eval)
-            return loss, grad, loss, grad
-        loss, grad = self._evaluate_active(theta_eval)
-        rows = self._rows[self._cur]
-        self.lib.scatter_rows(rows, loss.contiguous(), self._loss_full, n)
-        self.lib.scatter_rows(rows, grad.contiguous(), self._grad_full, n)
-        return loss, grad, self._loss_full, self._grad_full
-
-    def _step_stop_rule(self):
-        """step() with a stop rule.  While no seed has stopped: evaluate() + update as ever, plus the test.  After: gather the
-        evaluation point, solve / differentiate n_active rows, scatter loss / gradient, masked update, test."""
-        if self.n_active == 0:
-            return self._loss_full, self._grad_full
-        self._check_trace_room()
-        lib, B, n = self.lib, self.B, self.n_active
-        theta_eval = self._eval_point()
-        loss, grad, loss_full, grad_full = self._evaluate_stop_rule(theta_eval)
-        hook = self.event_hook
-        if hook is not None:
-            hook("update")
-        row_active = None if n == B else self._active      # (as of the last test: a seed that stops in this step is updated)
-        if self._ok is not None:                           # skip_unconverged: rows frozen for this step only
-            ok = self._ok.to(torch.int32)
-            row_active = ok if n == B else lib.scatter_rows(self._rows[self._cur], ok, self._active.clone(), n)
-            if self.count_unconverged:
-                self.n_unconverged = int(n - self._ok.sum().item())
-        self._update(grad_full, row_active, loss_full)
-        self.iter_idx += 1
-        if hook is not None:
-            hook("end")
-        if self._rows_path:
-            if self._true_rows is not None:      # flagged Nesterov rows only take the second evaluation (of the whole active batch)
-                loss, grad = loss.clone(), grad.clone()      # (the solver's buffers: the second evaluation writes them again)
-                flag = self._true_rows if n == B else self._true_rows[self._rows[self._cur][:n].long()]
-                l2, g2, _, _ = self._second_evaluation(lambda: self._evaluate_stop_rule(self.theta), flag)
-                loss, grad = torch.where(flag, l2, loss), torch.where(flag.unsqueeze(1), g2, grad)
-                loss_full, grad_full = loss, grad
-                if n < B:
-                    rows = self._rows[self._cur]
-                    loss_full = lib.scatter_rows(rows, loss, self._loss_full, n)
-                    grad_full = lib.scatter_rows(rows, grad, self._grad_full, n)
-        elif self.method == "Nesterov" and self.true_loss:      # QuadAlgorithm.py:487-492: the loss the reference's loop then tests
-            loss, grad, loss_full, grad_full = self._evaluate_stop_rule(self.theta)
-        self._append_trace(loss_full, grad_full, None if n == B else self._active)      # (active as of the previous test)
-        self._apply_stop_rule(loss, grad)
-        if self._loss_full is not None:
-            return self._loss_full, self._grad_full
-        return loss_full, grad_full
-
     # ---- several demonstrations per seed (mode='grouped') -----------------------------------------------------------------
     def _tile_demonstrations(self, ini_state, horizon, taus, waypoints, theta0):
         """The four per-row inputs with B = G * D rows (row g * D + d: demonstration d of group g).  Each may come per demonstration
@@ -1662,127 +1654,71 @@ class SparseDemoLearner:
             out[0] = out[0].unsqueeze(0).expand(B, -1).contiguous()
         return out
 
-    def _evaluate_grouped(self, theta):
-        """(loss [G], grad [G,p]): theta [G,p] expanded to the rows, the B rows evaluated as ever, their results summed per group
-        (lfsd_group_reduce: 0 plus the rows mask_unconverged left ok, ascending).  With method='LM' the group's H too."""
-        lib, D = self.lib, self.demos_per_seed
-        G, p = self.theta.shape
-        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] != p or theta.shape[0] not in (1, G) \
-                or theta.dtype != self.theta.dtype:
-            raise LfsdError("mode='grouped' evaluates theta [%d, %d] (or [1, %d], expanded to the groups) of dtype %s, got %s"
-                            % (G, p, p, self.theta.dtype, (tuple(theta.shape), theta.dtype) if isinstance(theta, torch.Tensor) else type(theta)))
-        if theta.shape[0] != G:      # (the index row -> row // D reaches G - 1: the gather must find G rows)
-            theta = theta.expand(G, p)
-        th = lib.gather_rows(self._group_of_row, theta.contiguous(), self._theta_rows, self.B)
-        self._ok = None
-        loss, grad = self._evaluate_rows(th)
-        self.row_loss, self.row_grad = loss, grad
-        if self.event_hook is not None:
-            self.event_hook("group_reduce")
-        row_ok = None if self._ok is None else self._ok.to(torch.int32)
-        H = self._H_t.contiguous() if self._lm is not None else None
-        if self._grp_out is None:
-            G, p, dt, dev = self.n_groups, grad.shape[1], self.theta.dtype, self.theta.device
-            new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
-            self._grp_out = (new(G), new(G, p), None if H is None else new(G, p, p), torch.empty(G, dtype=torch.int32, device=dev))
-        loss_g, grad_g, H_g, self.n_ok = lib.group_reduce(loss.contiguous(), grad.contiguous(), D, H=H, row_ok=row_ok, out=self._grp_out)
-        if H_g is not None:
-            self._H_rows, self._H_t = self._H_t, H_g      # (what lfsd_lm_step reads: the group's J^T J)
-        return loss_g, grad_g
-
-    def _step_grouped(self):
-        """step() of mode='grouped': evaluation point on G rows, evaluation and reduction (above), update on G rows."""
-        self._check_trace_room()
-        theta_eval = self._eval_point()
-        if self._tau is not None:
-            self._tau_pt = self._tau_eval_point()
-        if self._lmt is not None:      # (the evaluation point is (theta_trial, tau_trial))
-            self._tau_pt = self._lmt["trial"]
-        loss, grad = self._evaluate_grouped(theta_eval)
-        if self._tau is not None:
-            dtau = self._tau_gradient()
-        self._tau_pt = None
-        hook = self.event_hook
-        if hook is not None:
-            hook("update")
-        row_active = None
-        if self._ok is not None:      # skip_unconverged: a group none of whose demonstrations counted keeps every word of its state
-            row_active = (self.n_ok > 0).to(torch.int32)
-            if self.count_unconverged:
-                self.n_unconverged = int(self.B - self.n_ok.sum().item())
-        self._update(grad, row_active, loss)
-        if self._tau is not None:      # (every demonstration row owns its times: the mask is the rows', not the groups')
-            self._tau_update(dtau, None if self._ok is None else self._ok.to(torch.int32), self.iter_idx)
-        self.iter_idx += 1
-        if hook is not None:
-            hook("end")
-        second = self._true_rows is not None if self._rows_path else (self.method == "Nesterov" and bool(self.true_loss))
-        if second:                    # QuadAlgorithm.py:487-492: a second evaluation at theta, then reduced as the first
-            if not self._rows_path:
-                loss, grad = self._evaluate_grouped(self.theta)
-            else:                     # flagged Nesterov groups only take it; the others are left as their uniform learner leaves them
-                loss, grad, n_ok = loss.clone(), grad.clone(), self.n_ok.clone()
-                flag = self._true_rows
-                l2, g2 = self._second_evaluation(lambda: self._evaluate_grouped(self.theta), flag.repeat_interleave(self.demos_per_seed))
-                loss, grad = torch.where(flag, l2, loss), torch.where(flag.unsqueeze(1), g2, grad)
-                self.n_ok = torch.where(flag, self.n_ok, n_ok)
-        self._append_trace(loss, grad, None)
-        return loss, grad
-
+    # ---- one outer iteration, every mode ---------------------------------------------------------------------------------------
     def step(self):
-        """One outer iteration; returns (loss, grad) evaluated where the update rule needs them."""
-        if self.mode == "grouped":
-            return self._step_grouped()
-        if self._stop is not None:
-            return self._step_stop_rule()
+        """One outer iteration; returns (loss, grad) evaluated where the update rule needs them: per seed [B] (with a stop rule a
+        stopped seed keeps its last values), the sums [1] of mode='shared', the group sums [G] of mode='grouped'."""
+        lib, hook, B, n = self.lib, self.event_hook, self.B, self.n_active
+        if n == 0:                       # every seed has stopped: nothing is launched
+            return self._loss_full, self._grad_full
         self._check_trace_room()
+        shared, D = self.mode == "shared", self.demos_per_seed
+        rows = self._rows[self._cur] if n < B else None
+        full_size = lambda l, g: (l, g) if n == B else (self._loss_full, self._grad_full)
+        # the evaluation point: theta, the look-ahead or the LM trial point; for learned times their look-ahead or trial times
         theta_eval = self._eval_point()
-        self._ok = None
         if self._tau is not None:
             self._tau_pt = self._tau_eval_point()
-        if self._lmt is not None:      # (the evaluation point is (theta_trial, tau_trial))
+        if self._lmt is not None:
             self._tau_pt = self._lmt["trial"]
-        loss, grad = self.evaluate(theta_eval)
+        loss, grad = self._evaluate(theta_eval)
         if self._tau is not None:
             dtau = self._tau_gradient()
         self._tau_pt = None
-        hook = self.event_hook
         if hook is not None:
             hook("update")
-        row_active = None
-        if self.mode == "shared":
-            g = grad.sum(dim=0, keepdim=True)
-            l = loss.sum().reshape(1)
-            n_bad = (self.B - self._ok.sum()).to(g.dtype).reshape(1) if self._ok is not None else torch.zeros_like(l)
-            if self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-                buf = torch.cat([g.reshape(-1), l, n_bad])
-                torch.distributed.all_reduce(buf, group=self.pg)              # RCCL over xGMI on the GPU
-                g, l, n_bad = buf[:-2].reshape(1, -1), buf[-2:-1], buf[-1:]
-            grad_used, loss_out = g.contiguous(), l
-            self.n_bad_device = n_bad                                         # (device tensor: read it outside timed loops)
-            if self.skip_unconverged and self.count_unconverged:
-                self.n_unconverged = int(round(n_bad.item()))                 # over all ranks
-        else:
-            grad_used, loss_out = grad, loss
-            if self._ok is not None:
-                row_active = self._ok.to(torch.int32)
-                if self.count_unconverged:
-                    self.n_unconverged = int(self.B - self._ok.sum().item())
-        self._update(grad_used, row_active, loss_out)
-        if self._tau is not None:      # (the times are per row in every mode: in shared mode a frozen demonstration keeps its own)
-            self._tau_update(dtau, row_active if self.mode != "shared" or self._ok is None else self._ok.to(torch.int32), self.iter_idx)
+        if shared:
+            loss, grad = self._shared_sum(loss, grad, all_reduce=True)
+        # the rows of theta the update leaves alone: seeds stopped as of the last test (one that stops in this step is updated)
+        # and, under skip_unconverged, what mask_unconverged froze for this step -- a seed, or a group none of whose
+        # demonstrations counted (mode='shared' has the one theta: frozen demonstrations are left out of its sums)
+        row_active = None if n == B else self._active
+        rows_ok = None if self._ok is None else self._ok.to(torch.int32)
+        if rows_ok is not None:
+            if self.mode == "grouped":
+                row_active = (self.n_ok > 0).to(torch.int32)
+            elif not shared:
+                row_active = rows_ok if n == B else lib.scatter_rows(rows, rows_ok, self._active.clone(), n)
+            if self.count_unconverged:   # (one device->host read; in shared mode of the count over all ranks)
+                self.n_unconverged = int(round(self.n_bad_device.item())) if shared else int(n - self._ok.sum().item())
+        loss_out, grad_out = full_size(loss, grad)
+        self._update(grad_out, row_active, loss_out)
+        if self._tau is not None:        # (the times are per row in every mode: a frozen demonstration keeps its own)
+            self._tau_update(dtau, rows_ok, self.iter_idx)
         self.iter_idx += 1
         if hook is not None:
             hook("end")
-        if self._rows_path:
-            if self._true_rows is not None:      # flagged Nesterov rows only take the second evaluation (of the whole batch)
-                loss_out, grad_used = loss_out.clone(), grad_used.clone()      # (the solver's buffers: written again below)
-                l2, g2 = self._second_evaluation(lambda: self.evaluate(self.theta), self._true_rows)
-                loss_out = torch.where(self._true_rows, l2, loss_out)
-                grad_used = torch.where(self._true_rows.unsqueeze(1), g2, grad_used)
-        elif self.method == "Nesterov" and self.true_loss:
-            loss_out, grad_used = self.evaluate(self.theta)                   # QuadAlgorithm.py:487-492
-            if self.mode == "shared":
-                loss_out, grad_used = loss_out.sum().reshape(1), grad_used.sum(dim=0, keepdim=True)
-        self._append_trace(loss_out, grad_used, None)
-        return loss_out, grad_used
+        # QuadAlgorithm.py:487-492: Nesterov's true loss, a second evaluation at theta, reduced as the first
+        if self._true_rows is not None if self._rows_path else (self.method == "Nesterov" and bool(self.true_loss)):
+            if not self._rows_path:
+                loss, grad = self._evaluate(self.theta)
+                if shared:
+                    loss, grad = self._shared_sum(loss, grad, all_reduce=False)
+            else:       # flagged Nesterov rows (groups) only take it, the others are left as their uniform learner leaves them
+                first = (loss.clone(), grad.clone())      # (the solver's buffers: the second evaluation writes them again)
+                n_ok = self.n_ok.clone() if D else None
+                flag = self._true_rows if n == B else self._true_rows[rows[:n].long()]
+                l2, g2 = self._second_evaluation(lambda: self._evaluate(self.theta), flag.repeat_interleave(D) if D else flag)
+                loss, grad = torch.where(flag, l2, first[0]), torch.where(flag.unsqueeze(1), g2, first[1])
+                if D:
+                    self.n_ok = torch.where(flag, self.n_ok, n_ok)
+                if n < B:
+                    lib.scatter_rows(rows, loss, self._loss_full, n)
+                    lib.scatter_rows(rows, grad, self._grad_full, n)
+            loss_out, grad_out = full_size(loss, grad)
+        self._append_trace(loss_out, grad_out, None if n == B else self._active)      # (active as of the previous test)
+        if self._stop is not None:
+            self._apply_stop_rule(loss, grad)
+            if self._loss_full is not None:
+                return self._loss_full, self._grad_full
+        return loss_out, grad_out
